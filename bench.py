@@ -15,12 +15,20 @@ all-gathered over RCCL.  Steps run pipelined (slots 0-2 hold the same staged bat
 enqueued): step k+1's verify chain runs while step k's TxFlow chain tallies, as consecutive
 batches of a node do.  value = votes processed by all ranks / max-over-ranks time.
 
-Beside it: the end-to-end rate from the caller's host SoA columns (txv_submit_votes /
-txv_wait_votes, three batches in flight: staging copy + PCIe upload + kernels + results), the
-CPU baseline (the oracle's C restatement on every allowed host core, and 1 thread), the
-TxVoteMessage wire-decode leg and the C5 streaming leg.
+A plain run does only that: it sets up, warms up, times the K steps and prints the result line
+(with the in-pipeline stage times its steps record anyway).  --dump-outputs DIR also writes
+what the last timed step returned to its caller -- the per-vote statuses and the commit events
+-- as DIR/<name>.npy, so two builds can be compared output for output (the workload is
+deterministic by seed).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+With --full, beside it: the same chain run alone (standalone stage times, the tally's HBM rate),
+the end-to-end rate from the caller's host SoA columns (txv_submit_votes / txv_wait_votes, three
+batches in flight: staging copy + PCIe upload + kernels + results), the CPU baseline (the
+oracle's C restatement on every allowed host core, and 1 thread), the TxVoteMessage wire-decode
+leg, the C5 streaming, wire and long legs, the owner-rank route leg and C1 (each with its
+--no-* switch).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 """
 import argparse
@@ -1118,6 +1126,33 @@ TALLY_ALG_ADDED = 244     # B per ADDED vote: 128-byte accepted row written + 11
 # profiles/r03/tally_calib) + the 16 algorithmic bytes
 TALLY_LINE_VOTE = 128 + 16
 
+DUMP_MAX_BYTES = 56 << 20   # --dump-outputs: all ranks' files together stay under 64 MB
+
+
+def dump_outputs(path: str, st, ev, rank: int, world: int):
+    """--dump-outputs: what the last timed step handed its caller, as float arrays: status.npy
+    (one per vote: (added, err) status | fired bit << 7) and commit_vote_index / commit_tx_index /
+    commit_sum.npy (the commit events' columns, ordered by vote_index -- the batch position of the
+    vote that crossed 2/3, unique per event and fixed by the input -- so the files do not depend
+    on the order the device reports the events in).  An output above its share
+    of DUMP_MAX_BYTES is written as a fixed sample (seed 0, ascending rows), the rows taken
+    beside it as <name>_rows.npy.  At N>1 every rank writes its shard's as <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    sfx = ".npy" if world == 1 else f".rank{rank}.npy"
+    ev = ev[np.argsort(ev["vote_index"], kind="stable")]
+    cols = {"status": st.astype(np.float32)}
+    cols.update({f"commit_{f}": ev[f].astype(np.float64) for f in ("vote_index", "tx_index", "sum")})
+    budget = DUMP_MAX_BYTES // world // 2        # statuses and events: half each
+    for group in (["status"], ["commit_vote_index", "commit_tx_index", "commit_sum"]):
+        rows = len(cols[group[0]])
+        row_bytes = sum(cols[c].itemsize for c in group)
+        keep = None
+        if rows * row_bytes > budget:
+            keep = np.sort(np.random.default_rng(0).choice(rows, budget // (row_bytes + 8), replace=False))
+            np.save(os.path.join(path, group[0] + "_rows" + sfx), keep.astype(np.float64))
+        for c in group:
+            np.save(os.path.join(path, c + sfx), cols[c] if keep is None else cols[c][keep])
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -1164,7 +1199,16 @@ def main():
     ap.add_argument("--c5-long-only", action="store_true", help="profiling aid: only the one-long-TxFlow C5 leg")
     ap.add_argument("--c5-wire-only", action="store_true", help="profiling aid: only the C5 wire-bytes leg")
     ap.add_argument("--route-only", action="store_true", help="profiling aid: only the owner-rank route leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the correctness gate's step of its own, the chain run alone "
+                         "(standalone stage times, tally rate), the CPU baseline and the end-to-end, wire, C5, "
+                         "owner-route and C1 legs (each with its --no-* switch); off: the headline figure only "
+                         "(at N>1 the gate's step stays: the gathered state is checked after it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's statuses and commit events as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("TXV_BENCH_WATCHDOG"):   # debugging aid: every thread's stack on stderr periodically
         import faulthandler
         faulthandler.dump_traceback_later(int(os.environ["TXV_BENCH_WATCHDOG"]), repeat=True, file=sys.stderr)
@@ -1189,6 +1233,8 @@ def main():
         print(json.dumps(out), flush=True)
         return
 
+    if not args.full:       # a plain run: none of the legs beside the timed steps
+        args.no_cpu_baseline = args.no_c5 = args.no_c1 = args.no_route = args.no_wire = args.no_e2e = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = 0 if args.same_gpu else int(os.environ.get("LOCAL_RANK", "0"))
@@ -1252,17 +1298,24 @@ def main():
             k1a_ms.append(split[0]); k1b_ms.append(split[1])
 
     steps_rt.run(args.warmup)
+
     # correctness gate on the timed workload: every vote valid -> ADDED; every tx commits once,
     # with exactly n_vals - quorum + 1 fired votes per tx
-    st, ev = steps_rt.run(1)
-    n_added = int(np.count_nonzero((st & 0x7F) == T.ADDED))
-    n_fired = int(np.count_nonzero(st & 0x80))
-    quorum = ctx.total_power() * 2 // 3 + 1
-    exp_fired = wl.n_txs * (args.validators - quorum + 1)
-    if n_added != wl.n or len(ev) != wl.n_txs or n_fired != exp_fired or ctx.num_tx_sets() != wl.n_txs:
-        log(f"[rank {rank}] CORRECTNESS FAILURE: added {n_added}/{wl.n}, events {len(ev)}/{wl.n_txs}, "
-            f"fired {n_fired}/{exp_fired}, sets {ctx.num_tx_sets()}/{wl.n_txs}")
-        sys.exit(2)
+    def gate(st, ev):
+        n_added = int(np.count_nonzero((st & 0x7F) == T.ADDED))
+        n_fired = int(np.count_nonzero(st & 0x80))
+        quorum = ctx.total_power() * 2 // 3 + 1
+        exp_fired = wl.n_txs * (args.validators - quorum + 1)
+        if n_added != wl.n or len(ev) != wl.n_txs or n_fired != exp_fired or ctx.num_tx_sets() != wl.n_txs:
+            log(f"[rank {rank}] CORRECTNESS FAILURE: added {n_added}/{wl.n}, events {len(ev)}/{wl.n_txs}, "
+                f"fired {n_fired}/{exp_fired}, sets {ctx.num_tx_sets()}/{wl.n_txs}")
+            sys.exit(2)
+
+    # --full (and N>1, whose gathered state is checked below) gates on a step of its own before the
+    # timed region; a plain run reads the gate off its last timed step's results instead
+    gate_first = args.full or dist is not None
+    if gate_first:
+        gate(*steps_rt.run(1))
 
     if dist is not None:
         import torch
@@ -1288,12 +1341,16 @@ def main():
         torch.cuda.synchronize()
     ctx.sync()
     t0 = time.perf_counter()
-    steps_rt.run(args.steps, record)
+    st, ev = steps_rt.run(args.steps, record)
     ctx.sync()
     if dist is not None:
         torch.cuda.synchronize()
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if not gate_first:
+        gate(st, ev)
+    if args.dump_outputs:       # the last step's results, before its slot's buffers are reused
+        dump_outputs(args.dump_outputs, st, ev, rank, world)
     # RCCL: the per-step commit-state all-gather's device time on the exchange stream (events around
     # it, txflow_amd/pipeline.py), for the timed region's last `depth` steps (their slots' events)
     gather_ms = None
@@ -1313,17 +1370,18 @@ def main():
     value = total_votes * args.steps / elapsed
     r_ms, v_ms, t_ms = statistics.median(route_ms), statistics.median(verify_ms), statistics.median(tally_ms)
     # the same chain run alone (one step at a time, nothing beside it): per-stage device times
-    # without the pipeline's co-running kernels (the tally's HBM rate uses these)
+    # without the pipeline's co-running kernels (the tally's HBM rate uses these): --full only
     solo, solo_split = [], []
-    for _ in range(3):
-        ctx.reset_flow()
-        solo.append(ctx.run_staged(0, timed=True))
-        split = verify_split(ctx, 0)
-        if split:
-            solo_split.append(split)
-        ctx.fetch_staged(0, steps_rt.batches[0].n, ev_cap=steps_rt.ev_cap, out=steps_rt.st_buf[0], evs=steps_rt.ev_buf[0])
-    s_ms = [statistics.median(x[j] for x in solo) for j in range(4)]
-    s_split = [statistics.median(x[j] for x in solo_split) if solo_split else float("nan") for j in range(2)]
+    if args.full:
+        for _ in range(3):
+            ctx.reset_flow()
+            solo.append(ctx.run_staged(0, timed=True))
+            split = verify_split(ctx, 0)
+            if split:
+                solo_split.append(split)
+            ctx.fetch_staged(0, steps_rt.batches[0].n, ev_cap=steps_rt.ev_cap, out=steps_rt.st_buf[0], evs=steps_rt.ev_buf[0])
+        s_ms = [statistics.median(x[j] for x in solo) for j in range(4)]
+        s_split = [statistics.median(x[j] for x in solo_split) if solo_split else float("nan") for j in range(2)]
     if rank == 0:
         # roofline.achieved = algorithmic lane-ops of the verify pair per launch (W_ALG x votes) /
         # the pair's launch time (HIP events on the compute stream); the executed VALU lane-slots
@@ -1365,10 +1423,6 @@ def main():
                               "k1b": round(statistics.median(k1b_ms), 3) if k1b_ms else None, "tally_after_verify": round(t_ms, 3),
                               "note": "in the timed pipeline (HIP events on each stream): prep + SignBytes, K1a + K1b, "
                                       "verify end -> tally end (includes waiting for the flow stream)"},
-            "device_ms_standalone": {"prep": round(s_ms[0], 3), "verify": round(s_ms[1], 3), "k1a": round(s_split[0], 3) if solo_split else None,
-                                     "k1b": round(s_split[1], 3) if solo_split else None, "tally": round(s_ms[2], 3),
-                                     "chain": round(s_ms[3], 3),
-                                     "note": "one step alone after the timed region (no co-running kernels)"},
             "roofline": {"bound": "valu", "achieved": round(achieved / 1e12, 3), "peak": round(VALU_PEAK / 1e12, 3),
                          "unit": "Tlane-op/s (int32 VALU issue)", "frac": round(achieved / VALU_PEAK, 4),
                          "traffic": traffic, "kernel": "txv_k_challenge + txv_k_scalarmult_dyn (verify pair; txv_k_scalarmult_multi when TXV_K1B_DYNAMIC=0)",
@@ -1387,35 +1441,43 @@ def main():
                          "exec_achieved": None if exec_rate is None else round(exec_rate / 1e12, 3),
                          "exec_frac": None if exec_rate is None else round(exec_rate / VALU_PEAK, 4),
                          "pmc_source": pmc_src,
-                         "standalone": {"verify_ms": round(s_ms[1], 3),
-                                        "achieved": round(wl.n * w_alg / (s_ms[1] * 1e-3) / 1e12, 3),
-                                        "frac": round(wl.n * w_alg / (s_ms[1] * 1e-3) / VALU_PEAK, 4),
-                                        "note": "the same pair run alone after the timed region (no co-running "
-                                                "flow kernels)"},
                          "peak_source": "MI355X_MICROARCH.md: 256 CU x 4 SIMD x 32 lanes/clk x 2.4 GHz"},
-            "cpu_baseline": cpu,
+            "full": args.full,
+        }
+        if args.full:       # the figures of the chain run alone and the CPU baseline
+            out["device_ms_standalone"] = {
+                "prep": round(s_ms[0], 3), "verify": round(s_ms[1], 3), "k1a": round(s_split[0], 3) if solo_split else None,
+                "k1b": round(s_split[1], 3) if solo_split else None, "tally": round(s_ms[2], 3),
+                "chain": round(s_ms[3], 3),
+                "note": "one step alone after the timed region (no co-running kernels)"}
+            out["roofline"]["standalone"] = {
+                "verify_ms": round(s_ms[1], 3),
+                "achieved": round(wl.n * w_alg / (s_ms[1] * 1e-3) / 1e12, 3),
+                "frac": round(wl.n * w_alg / (s_ms[1] * 1e-3) / VALU_PEAK, 4),
+                "note": "the same pair run alone after the timed region (no co-running flow kernels)"}
+            out["cpu_baseline"] = cpu
             # the tally chain after verify (HBM-bound per BASELINE.md): bytes per launch from the same
             # PMC passes (2 x FETCH_SIZE + WRITE_SIZE of its kernels) over the standalone tally time
             # algorithmic bytes: 16 B per vote (set id, validator, verdict, pre-check,
             # status, cell) + 244 B per ADDED vote (its 128-byte accepted-vote row written, the 116
             # bytes of signature / height / time / TxKey it is made of read); every C2 vote is ADDED
-            "tally": {"ms": round(s_ms[2], 3), "hbm_bytes_per_launch": tally_bytes,
-                      "alg_bytes_per_launch": TALLY_ALG_VOTE * wl.n + TALLY_ALG_ADDED * wl.n,
-                      "alg_GBps": round((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n / (s_ms[2] * 1e-3) / 1e9, 1),
-                      "alg_frac_of_8TBps": round((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n / (s_ms[2] * 1e-3) / 8e12, 3),
-                      "traffic_over_alg": None if not tally_bytes else
-                      round(tally_bytes / ((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n), 3),
-                      "line_bound_bytes_per_launch": (TALLY_LINE_VOTE + TALLY_ALG_ADDED) * wl.n,
-                      "traffic_over_line_bound": None if not tally_bytes else
-                      round(tally_bytes / ((TALLY_LINE_VOTE + TALLY_ALG_ADDED) * wl.n), 3),
-                      "GBps": None if not tally_bytes else round(tally_bytes / (s_ms[2] * 1e-3) / 1e9, 1),
-                      "frac_of_8TBps": None if not tally_bytes else round(tally_bytes / (s_ms[2] * 1e-3) / 8e12, 3),
-                      "note": "hbm_bytes_per_launch from the committed PMC passes (2 x FETCH_SIZE + WRITE_SIZE of "
-                              "the tally kernels; the x2 holds for its 1- to 16-byte column reads and its random "
-                              "cell accesses too: profiles/r03/tally_calib); alg = 16 B/vote + 244 B per ADDED vote "
-                              "(BASELINE.md); line bound = the same with the vote's (set, validator) cell moved as "
-                              "the 128-B line a random access costs (C2's arrival order is shuffled)"},
-        }
+            out["tally"] = {
+                "ms": round(s_ms[2], 3), "hbm_bytes_per_launch": tally_bytes,
+                "alg_bytes_per_launch": TALLY_ALG_VOTE * wl.n + TALLY_ALG_ADDED * wl.n,
+                "alg_GBps": round((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n / (s_ms[2] * 1e-3) / 1e9, 1),
+                "alg_frac_of_8TBps": round((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n / (s_ms[2] * 1e-3) / 8e12, 3),
+                "traffic_over_alg": None if not tally_bytes else
+                round(tally_bytes / ((TALLY_ALG_VOTE + TALLY_ALG_ADDED) * wl.n), 3),
+                "line_bound_bytes_per_launch": (TALLY_LINE_VOTE + TALLY_ALG_ADDED) * wl.n,
+                "traffic_over_line_bound": None if not tally_bytes else
+                round(tally_bytes / ((TALLY_LINE_VOTE + TALLY_ALG_ADDED) * wl.n), 3),
+                "GBps": None if not tally_bytes else round(tally_bytes / (s_ms[2] * 1e-3) / 1e9, 1),
+                "frac_of_8TBps": None if not tally_bytes else round(tally_bytes / (s_ms[2] * 1e-3) / 8e12, 3),
+                "note": "hbm_bytes_per_launch from the committed PMC passes (2 x FETCH_SIZE + WRITE_SIZE of "
+                        "the tally kernels; the x2 holds for its 1- to 16-byte column reads and its random "
+                        "cell accesses too: profiles/r03/tally_calib); alg = 16 B/vote + 244 B per ADDED vote "
+                        "(BASELINE.md); line bound = the same with the vote's (set, validator) cell moved as "
+                        "the 128-B line a random access costs (C2's arrival order is shuffled)"}
         if world == 1 and not args.no_e2e:
             out["end_to_end"] = {
                 "note": "host SoA columns -> statuses + commit events (staging copy, PCIe upload, kernels, "

@@ -1,10 +1,12 @@
 #!/bin/bash
-# usage: prof_run.sh TAG  -- GPU tests, kernel trace, bench
+# usage: quick_cycle.sh TAG  -- GPU parity tests, kernel trace, bench with the end-to-end leg;
+# outputs under $OUT/TAG (default runs/TAG)
 set -o pipefail
 TAG=$1
 export TMPDIR=/tmp
-mkdir -p gpurun_out/$TAG
-timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread > gpurun_out/$TAG/gpu.log 2>&1 || { echo TESTFAIL; tail -30 gpurun_out/$TAG/gpu.log; exit 1; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/$TAG/kt -o kt --output-format csv -- python3 bench.py --no-cpu-baseline --no-c5 --no-c1 --no-wire --no-e2e --steps 5 --warmup 1 > gpurun_out/$TAG/kt_bench.json 2> gpurun_out/$TAG/kt_bench.err || { echo KTFAIL; grep -v "^[EW]20" gpurun_out/$TAG/kt_bench.err | tail; exit 2; }
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-c5 --no-c1 --no-wire --no-cpu-baseline > gpurun_out/$TAG/bench.log 2>&1 || { echo BENCHFAIL; tail gpurun_out/$TAG/bench.log; exit 3; }
-tail -2 gpurun_out/$TAG/gpu.log
+O=${OUT:-runs}/$TAG
+mkdir -p $O
+timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread > $O/gpu.log 2>&1 || { echo TESTFAIL; tail -30 $O/gpu.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-c5 --no-c1 --no-wire --no-e2e --steps 5 --warmup 1 > $O/kt_bench.json 2> $O/kt_bench.err || { echo KTFAIL; grep -v "^[EW]20" $O/kt_bench.err | tail; exit 2; }
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-c5 --no-c1 --no-wire --no-cpu-baseline > $O/bench.log 2>&1 || { echo BENCHFAIL; tail $O/bench.log; exit 3; }
+tail -2 $O/gpu.log
