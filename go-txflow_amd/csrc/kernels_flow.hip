@@ -496,14 +496,7 @@ struct NewSetAct {
 };
 
 // ------------------------------------------------------------------ tally
-__device__ __forceinline__ uint64_t cand_key(uint32_t stamp, uint32_t i) {
-  return ((uint64_t)(0xFFFFFFFFu - stamp) << 32) | i;
-}
-// the cell's first verified vote of this batch, or TXV_NONE (stale stamp = an earlier batch's)
-__device__ __forceinline__ uint32_t cand_of(uint64_t c, uint32_t stamp) {
-  return (uint32_t)(c >> 32) == 0xFFFFFFFFu - stamp ? (uint32_t)c : TXV_NONE;
-}
-
+// (cand_key / cand_of: txv_flow.h)
 // every vote's set id (after the new-id step); each verified pending vote posts its arrival
 // index to its (set, validator) cell: the cell then holds the FIRST verified vote of the group
 // (cells that already hold an accepted vote skip: their votes are decided without verification).
@@ -1107,6 +1100,12 @@ hipError_t txv_flow_new_ids(const FlowState* fs, const FlowBatch* b, hipStream_t
   return compact(NewSetPred{*fs, *b}, NewSetAct{*fs, *b}, b->n, b->blk, st);
 }
 
+const uint32_t* txv_flow_n_stamped(const FlowState* fs, const FlowBatch* b, uint32_t sets_bound) {
+  if (b->n < kStampCompactMin) return &fs->ctr->n_stamped;
+  sets_bound = std::min(sets_bound, fs->max_txs);
+  return fs->set_blk + (sets_bound + kScanItems - 1) / kScanItems;   // scan_top's total
+}
+
 // sets_bound: an upper bound on the set ids in use after this batch (the host's count as of
 // the last waited batch + this batch's votes, at most max_txs): the crossing step covers it
 hipError_t txv_flow_tally(const FlowState* fs, const FlowBatch* b, uint32_t sets_bound, hipStream_t st) {
@@ -1118,12 +1117,11 @@ hipError_t txv_flow_tally(const FlowState* fs, const FlowBatch* b, uint32_t sets
   const bool stamp_only = b->n >= kStampCompactMin;
   if (b->n && !TXV_SKIP(2))
     hipLaunchKernelGGL(txv_k_tally_resolve, dim3((b->n + 1023) / 1024), dim3(1024), 0, st, *fs, *b, stamp_only ? 1 : 0);
-  const uint32_t* n_stamped = &fs->ctr->n_stamped;
   if (stamp_only) {
     hipError_t e;
     if ((e = compact(StampPred{*fs, *b}, StampAct{*b}, sets_bound, fs->set_blk, st))) return e;
-    n_stamped = fs->set_blk + (sets_bound + kScanItems - 1) / kScanItems;   // scan_top's total
   }
+  const uint32_t* n_stamped = txv_flow_n_stamped(fs, b, sets_bound);
   // persistent waves over the batch's stamped sets (at most min(sets, votes) of them): one wave per set
   // TXV_CROSS_BLOCKS (experiment): the persistent one-wave blocks' cap (default 4096)
   static const uint32_t cross_cap = getenv("TXV_CROSS_BLOCKS") ? (uint32_t)atoi(getenv("TXV_CROSS_BLOCKS")) : 4096u;

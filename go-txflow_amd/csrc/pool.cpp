@@ -299,6 +299,8 @@ int pooldev_enqueue(txv_ctx* c, PoolDev* s, int slot, const txv_votes* v, const 
                     bool list_on, uint64_t live_ub, uint32_t n_upd, uint8_t* d_status_copy = nullptr,
                     void* then_stream = nullptr);
 int pooldev_stage(txv_ctx* c, PoolDev* s, int slot, uint32_t off, const txv_votes* v, const uint32_t* h_sizes);
+int pooldev_stage_dev(txv_ctx* c, PoolDev* s, int slot, uint32_t off, uint64_t ticket, uint32_t n);
+int update_list_keys(txv_ctx* c, uint64_t ticket, uint32_t n, std::vector<uint8_t>& keys, std::vector<uint32_t>& sizes);
 void pooldev_list_hint(PoolDev* s, uint64_t entries);
 int pooldev_finish(txv_ctx* c, PoolDev* s, int slot, const uint8_t** status, const uint8_t** keys, const uint32_t** sizes);
 int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t* sizes, const uint8_t* ins, uint32_t L);
@@ -1748,8 +1750,10 @@ int txv_pool_prepare(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_
 // before -- no flight is drained, nothing is copied back but the removal counts.  Size and
 // TxsBytes follow once the tickets submitted before are finished (txv_pool_check_wait,
 // txv_pool_sync, any reader).  Signatures > 64 bytes take the host path.
-int update_submit_dev(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint32_t* sizes) {
-  const uint32_t n = v->n;
+// stage(slot, off): the n entries into the flight slot's entries [off, off + n) -- uploaded from a
+// txv_votes batch (pooldev_stage) or copied from the list a context built in HBM (pooldev_stage_dev)
+extern "C++" template <class Stage>
+int update_staged_dev(txv_pool* p, txv_ctx* ctx, uint32_t n, Stage stage) {
   PTimer pt("update_submit");
   int r;
   // room for the next CheckTx batch beside the staged entries, so they ride with it instead of
@@ -1769,10 +1773,14 @@ int update_submit_dev(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint3
     p->pend_ctx = ctx;
   }
   pt.mark("prev");
-  if ((r = pooldev_stage(ctx, p->dev, p->pend_slot, p->pend_n, v, sizes))) return r;
+  if ((r = stage(p->pend_slot, p->pend_n))) return r;
   p->pend_n += n;
   pt.mark("stage");
   return TXV_OK;
+}
+int update_submit_dev(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint32_t* sizes) {
+  return update_staged_dev(p, ctx, v->n,
+                           [&](int slot, uint32_t off) { return pooldev_stage(ctx, p->dev, slot, off, v, sizes); });
 }
 
 // Update with the committed votes' keys and Size() values known (every flight and append
@@ -1829,6 +1837,28 @@ int txv_pool_update_submit(txv_pool* p, txv_ctx* ctx, int64_t height, const txv_
   p->height = height;
   if (!dsz.empty()) return update_submit_dev(p, ctx, v, dsz.data());
   return update_host(p, ctx, v, sig_full, sig_full_off);
+}
+
+// Update with the list the context built on the device for the batch of `ticket`
+// (txv_update_sink_enable): the contract of txv_pool_update_submit with that list as `committed`.
+// Lock order: the pool's, then the context's (txv_update_list, pooldev_stage_dev, update_list_keys).
+int txv_pool_update_fired(txv_pool* p, txv_ctx* ctx, int64_t height, uint64_t ticket) {
+  if (!p || !ctx) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  uint32_t n = 0;
+  int r = txv_update_list(ctx, ticket, nullptr, nullptr, nullptr, 0, &n);   // the mapped result: no wait
+  if (r) return r;                                                          // (overflow: the pool unchanged)
+  p->height = height;
+  if (!n) return TXV_OK;
+  if (dev_mode(p) && (!p->dev || pooldev_same_device(ctx, p->dev)))
+    return update_staged_dev(p, ctx, n, [&](int slot, uint32_t off) {
+      return pooldev_stage_dev(ctx, p->dev, slot, off, ticket, n);
+    });
+  // a host cache, or an engine on another GPU: the list's keys and sizes on the host
+  std::vector<uint8_t> keys;
+  std::vector<uint32_t> sizes;
+  if ((r = update_list_keys(ctx, ticket, n, keys, sizes))) return r;
+  return update_host_keys(p, ctx, reinterpret_cast<const Key*>(keys.data()), sizes.data(), n);
 }
 
 // Update applied when it returns: the device path's submission, then every ticket up to it

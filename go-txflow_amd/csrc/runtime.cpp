@@ -135,6 +135,15 @@ struct Slot {
   uint32_t* sink = nullptr;        // txv_set_commit_sink: packed commit state after each batch of this slot
   uint32_t sink_cap = 0;
   uint64_t ticket = 0;    // txv_submit_votes ticket in flight on this slot (0 = none)
+  // txv_update_sink_enable (submit ring slots): the batch's Update list, built behind its tally
+  // (kernels_update.hip): signatures [cap][16], lengths, TxVote.Size(), set ids; the result words
+  // (entries, fired sets, entries needed, overflow) in mapped host memory
+  uint32_t *u_sig = nullptr, *u_len = nullptr, *u_size = nullptr, *u_set = nullptr;
+  uint32_t *h_ures = nullptr, *m_ures = nullptr;
+  bool u_built = false;            // the slot's last chain built a list
+  uint64_t u_ticket = 0;           // the ticket that chain belongs to (0: none, e.g. a staged run)
+  hipEvent_t u_cons_ev = nullptr;  // a pool's device-to-device staging of the list (pooldev_stage_dev) has
+  bool u_cons = false;             // ended: the slot's next list build waits for it
 };
 
 }  // namespace
@@ -246,6 +255,12 @@ struct txv_ctx {
   uint64_t sets_seq = 0;            // run_seq n_sets_host belongs to (older summaries are not applied)
   uint64_t unfetched = 0;           // votes of batches run but not fetched yet (each may add sets)
   uint32_t poisoned = 0;            // TXV_FERR_* seen: every AddVote call fails until txv_reset_flow
+  // txv_update_sink_enable: entries per slot (0 = off) and the list builder's scratch (UpdateSink,
+  // txv_flow.h), shared by the slots: the builders run one after another on the flow stream
+  uint32_t upd_cap = 0;
+  uint64_t *d_upd_cnt = nullptr, *d_upd_blk = nullptr;
+  uint32_t *d_upd_sid = nullptr, *d_upd_fired = nullptr;
+  uint32_t* d_upd_keys = nullptr;   // [upd_cap][8] the list's keys (txv_pool_update_fired on a host-cache pool)
   // caller memory registered with txv_host_register (DMA'd without a staging copy)
   std::vector<std::pair<uintptr_t, uint64_t>> registered;
   std::mutex reg_mu;               // `registered` is changed under mu and reg_mu: read under either (the
@@ -507,6 +522,8 @@ int alloc_tally(txv_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_set_stamp, 0, (size_t)c->cfg.max_txs * 4, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_tab, 0, tab * sizeof(SetEntry), c->stream));
   c->stamp = 0;
+  if (c->d_upd_cnt)   // the Update list's columns are tagged with the stamp, which starts over
+    HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_ctr, 0, sizeof(FlowCounters), c->stream));
   c->seq_next = 0;
   c->n_sets_host = 0;
@@ -991,6 +1008,14 @@ int slot_kernel_ms(txv_ctx* c, Slot& s, float* ms) {
   return TXV_OK;
 }
 
+UpdateSink update_sink(const txv_ctx* c, const Slot& s) {
+  UpdateSink u{};
+  u.cap = c->upd_cap;
+  u.sig = s.u_sig; u.len = s.u_len; u.size = s.u_size; u.set = s.u_set; u.result = s.m_ures;
+  u.cnt = c->d_upd_cnt; u.sid = c->d_upd_sid; u.blk = c->d_upd_blk; u.fired = c->d_upd_fired;
+  return u;
+}
+
 // the whole AddVote chain of a staged batch: prep + SignBytes -> K1a/K1b verify (verify
 // stream), set keying -> new ids -> tally -> results into mapped host memory (flow stream)
 int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
@@ -1003,6 +1028,7 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     const FlowState fs0 = flow_state(c);
     HIP_TRY(c, txv_flow_init_cells(&fs0, (uint64_t)c->cfg.max_txs * std::max<uint32_t>(c->n_vals, 1), 0, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_set_stamp, 0, (size_t)c->cfg.max_txs * 4, c->stream));
+    if (c->d_upd_cnt) HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
     c->stamp = 0;
   }
   s.stamp = ++c->stamp;            // every run of a batch gets a stamp of its own
@@ -1014,6 +1040,8 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     for (Slot& o : c->slots)
       if (o.d_ev_tiles) HIP_TRY(c, hipMemsetAsync(o.d_ev_tiles, 0, (size_t)o.ev_tiles_n * sizeof(uint64_t), c->stream));
   s.run_seq = ++c->run_seq;
+  s.u_built = false;               // the slot's earlier list is gone with this run
+  s.u_ticket = 0;
   const FlowState fs = flow_state(c);
   const FlowBatch fb = flow_batch(c, s);
   // Three compute queues, so that batch k+1 verifies while batch k tallies and nothing but
@@ -1099,6 +1127,16 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     c->tally_ev_set = true;
   }
   if (s.sink) HIP_TRY(c, txv_flow_pack(&fs, s.sink, (s.sink_cap + 31) / 32, s.sink_cap, c->stream));
+  // txv_update_sink_enable: the batch's Update list (registries the builder ranks in LDS; a larger
+  // one leaves the slot without a list, which txv_update_list reports)
+  if (c->upd_cap && s.u_sig && c->n_vals <= TXV_UPD_MAX_VALS) {
+    if (s.u_cons) {                // a pool still copies the slot's previous list out
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, s.u_cons_ev, 0));
+      s.u_cons = false;
+    }
+    HIP_TRY(c, txv_flow_update_list(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), update_sink(c, s), c->stream));
+    s.u_built = true;
+  }
   HIP_TRY(c, hipEventRecord(s.ev[4], c->stream));
   s.ran = true;
   s.launched = true;
@@ -1355,6 +1393,7 @@ int submit_votes(txv_ctx* c, const txv_votes* v, uint64_t* ticket) {
   if ((r = stage_add(c, slot, v))) return r;
   if ((r = run_slot(c, slot, nullptr))) return r;
   s.ticket = t;
+  s.u_ticket = t;
   c->next_ticket = t + 1;
   *ticket = t;
   return TXV_OK;
@@ -1494,8 +1533,11 @@ void txv_destroy(txv_ctx* c) {
     dfree(s.d_entry); dfree(s.d_blk); dfree(s.d_ev_flag); dfree(s.d_mark); dfree(s.d_stamped); dfree(s.d_ev_tiles); hfree(s.h_ev); hfree(s.h_sum);
     hfree(s.h_fh); hfree(s.h_fs); hfree(s.h_fn); hfree(s.h_fo); hfree(s.h_fl); hfree(s.h_arena);
     dfree(s.d_fh); dfree(s.d_fs); dfree(s.d_fn); dfree(s.d_fo); dfree(s.d_fl); dfree(s.d_arena_th);
+    dfree(s.u_sig); dfree(s.u_len); dfree(s.u_size); dfree(s.u_set); hfree(s.h_ures);
+    if (s.u_cons_ev) (void)hipEventDestroy(s.u_cons_ev);
     for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
   }
+  dfree(c->d_upd_cnt); dfree(c->d_upd_blk); dfree(c->d_upd_sid); dfree(c->d_upd_fired); dfree(c->d_upd_keys);
   dfree(c->d_pubs); dfree(c->d_decode_ok); dfree(c->d_atables); dfree(c->d_vslot); dfree(c->d_addr); dfree(c->d_power);
   dfree(c->d_btable4); dfree(c->d_btable8); dfree(c->d_park); dfree(c->d_wctr); release_base_table(c->device, c->d_btable_wide); c->d_btable = nullptr; dfree(c->d_tmp_pubs); dfree(c->d_tmp_ok); dfree(c->d_tmp_tables); dfree(c->d_tmp_addr);
   dfree(c->d_cells); dfree(c->d_set_cross); dfree(c->d_set_sum);
@@ -2216,6 +2258,90 @@ int txv_set_commit_sink(txv_ctx* c, uint32_t slot, void* dst_dev, uint32_t n_set
   return TXV_OK;
 }
 
+int txv_update_sink_enable(txv_ctx* c, uint32_t max_entries) {
+  if (!c) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (uint32_t k = 0; k < kSubmitRing; ++k)
+    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
+  // no builder into, and no pool copy out of, the old buffers still pending
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    Slot& s = c->slots[k];
+    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
+    if (s.u_cons) HIP_TRY(c, hipEventSynchronize(s.u_cons_ev));
+    s.u_cons = false;
+    s.u_built = false;
+    s.u_ticket = 0;
+  }
+  c->upd_cap = 0;
+  const size_t m = max_entries, nb = c->cfg.max_batch;
+  int r;
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    Slot& s = c->slots[k];
+    if ((r = dalloc(c, &s.u_sig, 16 * m)) || (r = dalloc(c, &s.u_len, m)) || (r = dalloc(c, &s.u_size, m)) ||
+        (r = dalloc(c, &s.u_set, m)) || (r = halloc_mapped(c, &s.h_ures, &s.m_ures, m ? 4 : 0)))
+      return r;
+    if (m && !s.u_cons_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.u_cons_ev, hipEventDisableTiming));
+  }
+  if ((r = dalloc(c, &c->d_upd_cnt, m ? nb : 0)) || (r = dalloc(c, &c->d_upd_sid, m ? nb : 0)) ||
+      (r = dalloc(c, &c->d_upd_blk, m ? (nb + 1023) / 1024 + 1 : 0)) || (r = dalloc(c, &c->d_upd_fired, m ? 2 * nb : 0)) ||
+      (r = dalloc(c, &c->d_upd_keys, 8 * m)))
+    return r;
+  if (!m) return TXV_OK;
+  HIP_TRY(c, hipMemset(c->d_upd_cnt, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
+  c->upd_cap = max_entries;
+  return TXV_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the slot holding `ticket`'s Update list (c->mu held), or null with c->err set; *n = its entries.
+// TXV_ECAPACITY (*n = the entries it needs) when the batch overflowed the sink.
+int update_list_slot(txv_ctx* c, uint64_t ticket, Slot** out, uint32_t* n) {
+  *out = nullptr;
+  *n = 0;
+  if (!c->upd_cap) { c->err = "the Update sink is off (txv_update_sink_enable)"; return TXV_ESTATE; }
+  if (!ticket) return TXV_EINVAL;
+  Slot& s = c->slots[(ticket - 1) % kSubmitRing];
+  if (s.u_ticket != ticket) { c->err = "no Update list for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
+  if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
+  if (!s.u_built) { c->err = "no Update list was built: more than 1024 validators"; return TXV_ESTATE; }
+  uint32_t res[4];
+  memcpy(res, (const void*)s.h_ures, sizeof res);   // written over PCIe before the slot's ev[4]
+  *out = &s;
+  if (res[3]) {
+    *n = res[2];
+    c->err = "the batch's Update list exceeds the sink's max_entries";
+    return TXV_ECAPACITY;
+  }
+  *n = res[0];
+  return TXV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int txv_update_list(txv_ctx* c, uint64_t ticket, uint8_t* sig_out, uint32_t* size_out, uint32_t* set_out, uint32_t cap,
+                    uint32_t* n_out) {
+  if (!c) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  Slot* s;
+  uint32_t n;
+  const int r = update_list_slot(c, ticket, &s, &n);
+  if (n_out) *n_out = n;
+  if (r) return r;
+  if (!n || (!sig_out && !size_out && !set_out)) return TXV_OK;
+  if (cap < n) { c->err = "txv_update_list: the output arrays are smaller than the list"; return TXV_ECAPACITY; }
+  if (sig_out) HIP_TRY(c, hipMemcpy(sig_out, s->u_sig, (size_t)n * 64, hipMemcpyDeviceToHost));
+  if (size_out) HIP_TRY(c, hipMemcpy(size_out, s->u_size, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (set_out) HIP_TRY(c, hipMemcpy(set_out, s->u_set, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return TXV_OK;
+}
+
 int txv_slot_kernel_ms(txv_ctx* c, uint32_t slot, float* ms4) {
   if (!c || !ms4 || slot >= kStagedSlots) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
@@ -2641,6 +2767,7 @@ int txv_submit_routed(txv_ctx* c, const void* buf_dev, const txv_route_meta* met
   if ((r = stage_routed(c, slot, static_cast<const uint8_t*>(buf_dev), meta))) return r;
   if ((r = run_slot(c, slot, nullptr))) return r;
   s.ticket = t;
+  s.u_ticket = t;
   c->next_ticket = t + 1;
   *ticket = t;
   return TXV_OK;
@@ -4089,6 +4216,13 @@ hipStream_t engine_stream(txv_ctx* c, const PoolDev* s) {
   return s->on_ctx == 2 ? c->key_stream : s->on_ctx == 3 ? c->copy_stream : s->st;
 }
 
+// the stream a flight's entries are uploaded on (ks: the engine's)
+hipStream_t upload_stream(txv_ctx* c, hipStream_t ks) {
+  // TXV_POOL_UPLOAD_STREAM (experiment): 1 (default) the copy stream, 0 the engine's stream itself
+  static const int up_mode = getenv("TXV_POOL_UPLOAD_STREAM") ? atoi(getenv("TXV_POOL_UPLOAD_STREAM")) : 1;
+  return up_mode ? c->copy_stream : ks;
+}
+
 // n votes of a txv_votes batch into flight f's entries [off, off + n): signatures uploaded -- from
 // caller memory registered with txv_host_register (which must stay valid until the finish) or
 // through the slot's pinned staging -- on the context's copy stream (the DMA does not hold up the
@@ -4096,9 +4230,7 @@ hipStream_t engine_stream(txv_ctx* c, const PoolDev* s) {
 // TxVote.Size(); with key, keyed on stream ks once uploaded
 int upload_votes(txv_ctx* c, PoolDev::Flight& f, hipStream_t ks, const txv_votes* v, uint32_t off, uint32_t n,
                  const uint32_t* h_sizes, bool key) {
-  // TXV_POOL_UPLOAD_STREAM (experiment): 1 (default) the copy stream, 0 the engine's stream itself
-  static const int up_mode = getenv("TXV_POOL_UPLOAD_STREAM") ? atoi(getenv("TXV_POOL_UPLOAD_STREAM")) : 1;
-  hipStream_t us = up_mode ? c->copy_stream : ks;
+  hipStream_t us = upload_stream(c, ks);
   bool reg;
   {
     std::lock_guard<std::mutex> lk(c->reg_mu);
@@ -4134,6 +4266,52 @@ int pooldev_stage(txv_ctx* c, PoolDev* s, int slot, uint32_t off, const txv_vote
   if (!v->n) return TXV_OK;
   if ((uint64_t)off + v->n > s->cap_n) { c->err = "pool device batch above its capacity"; return TXV_ECAPACITY; }
   return upload_votes(c, s->fl[slot], engine_stream(c, s), v, off, v->n, h_sizes, false);
+}
+
+// pooldev_stage with the entries already in HBM: the n entries of the Update list the context built
+// for `ticket` (txv_update_sink_enable; the ticket waited, so the list is complete) copied device
+// to device into the flight's entries [off, off + n) on the upload stream -- no host copy, no
+// wait.  The context slot's next list build waits for the copies (u_cons_ev, as cons_ev above).
+int pooldev_stage_dev(txv_ctx* c, PoolDev* s, int slot, uint32_t off, uint64_t ticket, uint32_t n) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!n) return TXV_OK;
+  if ((uint64_t)off + n > s->cap_n) { c->err = "pool device batch above its capacity"; return TXV_ECAPACITY; }
+  std::lock_guard<std::mutex> g(c->mu);
+  Slot* src;
+  uint32_t have;
+  if (int r = update_list_slot(c, ticket, &src, &have)) return r;
+  if (have != n) { c->err = "the Update list changed under txv_pool_update_fired"; return TXV_ESTATE; }
+  PoolDev::Flight& f = s->fl[slot];
+  hipStream_t us = upload_stream(c, engine_stream(c, s));
+  f.occ = 0;
+  if (f.cons) HIP_TRY(c, hipStreamWaitEvent(us, f.cons_ev, 0));   // a TxFlow chain's reads of the slot first
+  HIP_TRY(c, hipMemcpyAsync(f.d_sig + (size_t)off * 16, src->u_sig, (size_t)n * 64, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipMemcpyAsync(f.d_len + off, src->u_len, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipMemcpyAsync(f.d_sizes + off, src->u_size, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipEventRecord(f.up_ev, us));
+  HIP_TRY(c, hipEventRecord(src->u_cons_ev, us));
+  src->u_cons = true;
+  return TXV_OK;
+}
+
+// the same list as (txVoteKey, Size()) pairs on the host, for a pool that keeps its cache there:
+// keyed on the GPU, copied back, waited for
+int update_list_keys(txv_ctx* c, uint64_t ticket, uint32_t n, std::vector<uint8_t>& keys, std::vector<uint32_t>& sizes) {
+  keys.assign((size_t)n * 32, 0);
+  sizes.assign(n, 0);
+  if (!n) return TXV_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  Slot* src;
+  uint32_t have;
+  if (int r = update_list_slot(c, ticket, &src, &have)) return r;
+  if (have != n) { c->err = "the Update list changed under txv_pool_update_fired"; return TXV_ESTATE; }
+  hipStream_t ks = c->key_stream;
+  HIP_TRY(c, txv_launch_sig_keys(src->u_sig, src->u_len, n, c->d_upd_keys, ks));
+  HIP_TRY(c, hipMemcpyAsync(keys.data(), c->d_upd_keys, (size_t)n * 32, hipMemcpyDeviceToHost, ks));
+  HIP_TRY(c, hipMemcpyAsync(sizes.data(), src->u_size, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
+  HIP_TRY(c, hipStreamSynchronize(ks));
+  return TXV_OK;
 }
 
 // one batch's decisions enqueued on the engine's stream into flight slot `slot` (whose previous
@@ -4375,6 +4553,7 @@ int submit_checked_run(txv_ctx* c, uint32_t slot, const txv_votes* v, const uint
   if ((r = run_slot(c, slot, nullptr))) return r;
   const uint64_t t = c->next_ticket;
   s.ticket = t;
+  s.u_ticket = t;
   c->next_ticket = t + 1;
   *ticket = t;
   return TXV_OK;

@@ -192,6 +192,37 @@ struct FlowBatch {
   FlowSummary* summary_host;
 };
 
+// the candidate word of a cell: (~stamp << 32 | arrival index), so an atomic min keeps the first
+// verified vote of the newest batch and a stale stamp reads as "none"
+__device__ __forceinline__ uint64_t cand_key(uint32_t stamp, uint32_t i) {
+  return ((uint64_t)(0xFFFFFFFFu - stamp) << 32) | i;
+}
+// the cell's first verified vote of this batch, or TXV_NONE (stale stamp = an earlier batch's)
+__device__ __forceinline__ uint32_t cand_of(uint64_t c, uint32_t stamp) {
+  return (uint32_t)(c >> 32) == 0xFFFFFFFFu - stamp ? (uint32_t)c : TXV_NONE;
+}
+
+// TxVotePool.Update's argument for one batch, built on the device (kernels_update.hip): the sets
+// that fired in the batch, ordered by the arrival index of their last fired vote, each set's
+// accepted votes so far as one block in arrival (sequence) order -- txflow/service.go:216-227's
+// `txV.Update(height, set.GetVotes())` once per batch (tests/test_update_cadence.py).
+#define TXV_UPD_MAX_VALS 1024u    // accepted votes of a set ranked in LDS
+struct UpdateSink {
+  uint32_t cap;                   // entries the output columns hold
+  uint32_t pad0;
+  uint32_t* sig;                  // [cap][16] signature words, row-major (PoolDev::Flight::d_sig)
+  uint32_t* len;                  // [cap] signature lengths (all 64)
+  uint32_t* size;                 // [cap] TxVote.Size()
+  uint32_t* set;                  // [cap] set id of each entry
+  uint32_t* result;               // mapped host memory: n_entries, n_sets, needed, err
+  // scratch shared by every slot of the context (the builders run in flow-stream order)
+  uint64_t* cnt;                  // [max_batch] (stamp << 32 | accepted votes) of the set whose last fired
+                                  // vote arrived at this index (stamp-tagged: never cleared)
+  uint32_t* sid;                  // [max_batch] that set's id
+  uint64_t* blk;                  // [ceil(max_batch / 1024) + 1] scan blocks: (fired sets << 32 | entries)
+  uint32_t* fired;                // [max_batch][2] (set id, first entry) of the fired sets in list order
+};
+
 extern "C" {
 // the whole AddVote chain of one batch except SignBytes and verify, on two streams:
 // prep (pre-checks, validator lookup, signature transpose, SignBytes lengths: everything the
@@ -204,6 +235,12 @@ hipError_t txv_flow_route(const FlowState* fs, const FlowBatch* b, hipStream_t s
 hipError_t txv_flow_new_ids(const FlowState* fs, const FlowBatch* b, hipStream_t st);
 // ... then, after K1a/K1b wrote b->ok and the new ids exist: tally, commit events, statuses
 hipError_t txv_flow_tally(const FlowState* fs, const FlowBatch* b, uint32_t sets_bound, hipStream_t st);
+// where that tally left the length of b->stamped (the counter, or the compaction's total for the
+// large batches that list their stamped sets by compaction)
+const uint32_t* txv_flow_n_stamped(const FlowState* fs, const FlowBatch* b, uint32_t sets_bound);
+// after the tally, on the same stream: the batch's Update list into the sink (kernels_update.hip)
+hipError_t txv_flow_update_list(const FlowState* fs, const FlowBatch* b, const uint32_t* n_stamped, UpdateSink u,
+                                hipStream_t st);
 // forget every TxVoteSet (keep_ids = 0) or empty them keeping their ids (keep_ids = 1)
 hipError_t txv_flow_reset(const FlowState* fs, int keep_ids, hipStream_t st);
 // cells of the first `cells` (set, validator) pairs: every candidate forgotten (cand = ~0), and

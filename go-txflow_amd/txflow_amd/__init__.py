@@ -51,6 +51,21 @@ class TxvInfraError(RuntimeError):
     pass
 
 
+E_STATE = -1       # TXV_ESTATE
+E_CAPACITY = -28   # TXV_ECAPACITY
+
+
+class UpdateListError(TxvInfraError):
+    """Context.update_list / TxVotePool.update_fired: no list to read (rc = E_STATE: sink off,
+    ticket not waited, slot reused) or the batch's list overflowed the sink (rc = E_CAPACITY,
+    n = the entries it needs)"""
+
+    def __init__(self, what, rc, n, msg):
+        super().__init__(f"{what} failed ({rc}): {msg}")
+        self.rc = rc
+        self.n = n
+
+
 class _Cfg(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("max_batch", ctypes.c_uint32), ("max_txs", ctypes.c_uint32),
                 ("max_validators", ctypes.c_uint32), ("max_accepted", ctypes.c_uint32),
@@ -196,6 +211,9 @@ def lib():
             "txv_route_pack_host": ([ctypes.POINTER(_Votes), vp, u32, vp, ctypes.c_uint64, vp], ctypes.c_int),
             "txv_route_view": ([vp, ctypes.c_uint64, ctypes.POINTER(_Votes)], ctypes.c_int),
             "txv_submit_routed": ([vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_update_sink_enable": ([vp, u32], ctypes.c_int),
+            "txv_update_list": ([vp, ctypes.c_uint64, vp, vp, vp, u32, ctypes.POINTER(u32)], ctypes.c_int),
+            "txv_pool_update_fired": ([vp, vp, i64, ctypes.c_uint64], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -223,7 +241,8 @@ EXPORTED_SYMBOLS = [
     "txv_commit_state_unpack", "txv_set_commit_sink", "txv_slot_kernel_ms", "txv_slot_verify_ms", "txv_flow_stream",
     "txv_ingest_msgs", "txv_ingest_submit", "txv_ingest_wait", "txv_pool_prepare",
     "txv_ingest_decode", "txv_ingest_admit", "txv_route_bytes", "txv_route_admitted", "txv_route_checked", "txv_route_pack_host",
-    "txv_route_view", "txv_submit_routed", "txv_ingest_admit_submit", "txv_ingest_admit_finish"]
+    "txv_route_view", "txv_submit_routed", "txv_ingest_admit_submit", "txv_ingest_admit_finish",
+    "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -655,6 +674,29 @@ class Context:
                   "txv_wait_votes")
         self._inflight.pop(ticket, None)
         return out[:n], evs[:min(nev.value, ev_cap)]
+
+    def enable_update_sink(self, max_entries: int):
+        """txv_update_sink_enable: every submitted batch leaves its TxVotePool.Update list (the
+        sets it fired, by last fired vote; each set's accepted votes in arrival order) in HBM, up
+        to max_entries entries per batch; 0 turns it off"""
+        self._chk(lib().txv_update_sink_enable(self._h, max_entries), "txv_update_sink_enable")
+
+    def update_list(self, ticket: int):
+        """txv_update_list for a waited ticket: (sig [n, 64] u8, TxVote.Size() [n] u32, set id [n]
+        u32).  UpdateListError (rc = TXV_ESTATE / TXV_ECAPACITY, n = entries needed) when there is
+        no list to read."""
+        n = ctypes.c_uint32()
+        rc = lib().txv_update_list(self._h, ticket, None, None, None, 0, ctypes.byref(n))
+        if rc < 0:
+            raise UpdateListError("txv_update_list", rc, n.value, lib().txv_last_error(self._h).decode())
+        k = n.value
+        sig = np.zeros((k, 64), np.uint8); size = np.zeros(k, np.uint32); sets = np.zeros(k, np.uint32)
+        if k:
+            rc = lib().txv_update_list(self._h, ticket, sig.ctypes.data, size.ctypes.data, sets.ctypes.data, k,
+                                       ctypes.byref(n))
+            if rc < 0:
+                raise UpdateListError("txv_update_list", rc, n.value, lib().txv_last_error(self._h).decode())
+        return sig, size, sets
 
     def get_votes(self, txhash: bytes):
         """TxVoteSet.GetVotes: [(validator index, vote sequence number, signature bytes)] in
@@ -1207,6 +1249,16 @@ class TxVotePool:
         refs = self.__dict__.setdefault("_upd_refs", [])
         refs.append((batch, full, off, vs))
         del refs[:-5]
+
+    def update_fired(self, ctx: "Context", height: int, ticket: int):
+        """txv_pool_update_fired: update_submit with the list ctx built on the device for the
+        waited batch `ticket` (Context.enable_update_sink) -- nothing gathered or uploaded by the
+        host; sync() applies it"""
+        rc = lib().txv_pool_update_fired(self._h, ctx._h, height, ticket)
+        if rc < 0:
+            n = ctypes.c_uint32()
+            lib().txv_update_list(ctx._h, ticket, None, None, None, 0, ctypes.byref(n))
+            raise UpdateListError("txv_pool_update_fired", rc, n.value, lib().txv_last_error(ctx._h).decode())
 
     def reap(self, max_txs: int = -1):
         """ReapMaxTxs: ([k, 32] keys, [k] sizes) in pool order"""

@@ -234,6 +234,28 @@ int txv_wait_votes(txv_ctx* ctx, uint64_t ticket, uint8_t* status_out, txv_commi
 int txv_get_votes(txv_ctx* ctx, const uint8_t* txhash, uint32_t len, uint32_t* val_out, uint64_t* seq_out,
                   uint8_t* sig_out, uint32_t cap, uint32_t* n_out);
 
+/* TxVotePool.Update's argument built on the device (txflow/service.go:216-227: after every fired
+ * vote the commit path runs txV.Update(height, set.GetVotes())).  With the sink enabled, every
+ * batch of the submit ring (txv_submit_votes, txv_submit_checked, txv_submit_routed, and
+ * txv_add_votes through them) leaves, behind its tally, the list one Update per batch takes: the
+ * sets that fired in the batch, ordered by the arrival index of their last fired vote, each set's
+ * accepted votes so far -- as of the end of that batch -- in arrival order as one block.  That
+ * list leaves the pool as the reference's Update after every fired vote does.  Per entry: the 64
+ * signature bytes, TxVote.Size() and the set id (tx_index of the commit events).
+ * txv_update_sink_enable: per-slot buffers of max_entries entries for the four-slot ring; 0
+ *   disables and frees them (the default: no list is built).  Waits for the chains in flight;
+ *   TXV_ESTATE while a submitted batch has not been waited for.
+ * txv_update_list: the list of the batch `ticket` names, readable from the return of
+ *   txv_wait_votes(ticket) until the slot's next batch is submitted (four submits later).  Any
+ *   output may be NULL; *n_out = entries.  TXV_ESTATE when the sink is off, the ticket has not
+ *   been waited for, its slot was reused, or the registry has more than 1024 validators (no list
+ *   is built then); TXV_ECAPACITY when the batch's list exceeded max_entries (*n_out = the entries
+ *   it needs; the batch's TxFlow results are not affected) or `cap` is below the list's length
+ *   (*n_out = the length; nothing written). */
+int txv_update_sink_enable(txv_ctx* ctx, uint32_t max_entries);
+int txv_update_list(txv_ctx* ctx, uint64_t ticket, uint8_t* sig_out, uint32_t* size_out, uint32_t* set_out,
+                    uint32_t cap, uint32_t* n_out);
+
 /* Tally readers for the TxVoteSet of txhash.  Returns 1 if the set exists, 0 if not. */
 int txv_query_tx(txv_ctx* ctx, const uint8_t* txhash, uint32_t len, int64_t* sum, uint8_t* maj23);
 /* the same for n TxHashes (txhash + off[i], len[i] bytes); any output may be NULL; txkey_out
@@ -503,6 +525,17 @@ int txv_pool_update_keys(txv_pool* pool, txv_ctx* ctx, int64_t height, const uin
  * txflow/service.go:224-227 -> txvotepool.go:329-359 */
 int txv_pool_update_submit(txv_pool* pool, txv_ctx* ctx, int64_t height, const txv_votes* committed,
                            const uint8_t* sig_full, const uint64_t* sig_full_off);
+/* txv_pool_update_submit with the list ctx built on the device for the batch of `ticket` as
+ * `committed` (txv_update_sink_enable; the ticket waited for): "apply the Update for what this
+ * batch committed" without the host listing the votes.  With TXV_POOL_DEVICE_CACHE on ctx's
+ * device the entries are copied device to device into the engine's pending slot -- no signature
+ * crosses the link, the call waits for nothing -- and applied ahead of the next CheckTx batch, or
+ * at txv_pool_sync (txv_pool_update_fired then txv_pool_sync: applied on return).  A pool with a
+ * host cache, or an engine on another GPU, gets the list's keys (hashed on ctx's GPU) and sizes
+ * and applies them at once.  An empty list only sets the height.  The errors of txv_update_list;
+ * on any of them (TXV_ECAPACITY: the list overflowed the sink) the pool is unchanged.
+ * txflow/service.go:216-227 -> txvotepool.go:329-359 */
+int txv_pool_update_fired(txv_pool* pool, txv_ctx* ctx, int64_t height, uint64_t ticket);
 /* ReapMaxTxs(max) in pool order: keys (32 B) and TxVote.Size of the reaped entries; the
  * reference loop condition `len(txs) <= max` reaps max + 1 entries when available; max < 0 = all.
  * keys_out / sizes_out capacity `cap`; *n_out = entries reaped (may exceed cap: truncated). */
@@ -513,11 +546,13 @@ int txv_pool_flush(txv_pool* pool);
 int64_t txv_pool_size(txv_pool* pool);
 int64_t txv_pool_txs_bytes(txv_pool* pool);
 int64_t txv_pool_height(txv_pool* pool);
-/* With TXV_POOL_DEVICE_CACHE the votes a device batch admitted are appended to the pool list by a
- * thread of the pool's own on the checking context's host workers, while the next batch is
- * decided (Size and TxsBytes count them at once; every call that reads the pool list waits for
- * it).  txv_pool_sync waits for those appends: call it before txv_destroy of that context when
- * the pool outlives it (txv_pool_free waits too). */
+/* With TXV_POOL_DEVICE_CACHE the pool list lives in HBM beside the cache: a device batch's engine
+ * chain appends the votes it admitted and removes an Update's committed ones in submission order
+ * (there is no appender thread); Size and TxsBytes follow each finished batch's counts, and every
+ * call that reads the pool list or cache finishes the submitted batches first.  txv_pool_sync
+ * applies the Updates submitted so far (txv_pool_update_submit, txv_pool_update_fired): staged
+ * entries are decided and every submitted batch up to them finished.  Call it before txv_destroy
+ * of the context the pool last ran on when the pool outlives it (txv_pool_free waits too). */
 int txv_pool_sync(txv_pool* pool);
 /* LRU cache keys front (oldest) to back; *n_out = cache length (test hook: cache_test.go). */
 int txv_pool_cache_keys(txv_pool* pool, uint8_t* keys_out, uint64_t cap, uint64_t* n_out);
