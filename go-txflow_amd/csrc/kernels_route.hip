@@ -14,8 +14,9 @@
 //            TxHash per shard (the receiver's SignBytes column bound)
 //   scan     one block per shard: exclusive scans of those per-wave counts / bytes over the waves
 //            (arrival order), the shard's totals, its buffer header and the 16 zero bytes behind
-//            its TxHash arena, its meta entry in mapped host memory
-//   scatter  each admitted vote's rank inside its shard = the wave's prefix + its rank among the
+//            its TxHash arena, its meta entry in mapped host memory; a shard whose total exceeds the
+//            stride is refused instead (nothing written but its meta, reserved = 1)
+//   scatter  (votes of a refused shard skipped) each admitted vote's rank inside its shard = the wave's prefix + its rank among the
 //            wave's lanes of that shard (ballot), its TxHash arena offset likewise (a masked wave
 //            scan of the lengths); every column written at that position, the TxHash copied
 // No atomics on shared words, no host round trip between the launches.
@@ -114,20 +115,26 @@ __global__ void __launch_bounds__(1024) txv_k_route_scan(RouteArgs a) {
   const uint64_t n = carry_c, ab = carry_b;
   uint64_t off[txv_route::kNCols];
   const uint64_t total = txv_route::layout(n, ab, a.flags, off);
+  // the stride guard: a shard's buffer holds the sum of its votes' TxHash lengths, which votes
+  // sharing TxHash offsets push past any bound taken from the arena extent.  A shard over its
+  // stride gets no byte written (the bytes behind dst + s * stride + stride are the next shard's,
+  // another ticket's or nobody's); its meta still tells the size it needs
+  const bool fits = total <= a.stride;   // (block-uniform)
   uint8_t* base = a.dst + (size_t)s * a.stride;
-  if (threadIdx.x < 8) {
+  if (fits && threadIdx.x < 8) {
     const uint64_t hdr[8] = {txv_route::kMagic, n, ab, a.flags, a.maxhl[s], total, 0, 0};
     reinterpret_cast<uint64_t*>(base)[threadIdx.x] = hdr[threadIdx.x];
   }
-  if (threadIdx.x < 16) base[off[txv_route::kArena] + ab + threadIdx.x] = 0;
+  if (fits && threadIdx.x < 16) base[off[txv_route::kArena] + ab + threadIdx.x] = 0;
+  if (s == 0 && threadIdx.x == 0 && a.pool_err) *a.pool_err_host = *a.pool_err;
   if (threadIdx.x == 0) {
-    a.tot[2 * s] = n;
+    a.tot[2 * s] = fits ? n : txv_route::kRefused;
     a.tot[2 * s + 1] = ab;
     txv_route_meta m;
     m.n = (uint32_t)n;
     m.max_txhash_len = a.maxhl[s];
     m.flags = a.flags;
-    m.reserved = 0;
+    m.reserved = fits ? 0u : 1u;
     m.arena_bytes = ab;
     m.bytes = total;
     a.meta[s] = m;
@@ -153,10 +160,12 @@ __global__ void __launch_bounds__(256) txv_k_route_scatter(RouteArgs a) {
     }
   }
   if (r == 0xFFu) return;
+  const uint64_t tn = a.tot[2 * r];
+  if (tn == txv_route::kRefused) return;   // the scan refused the shard: its region stays untouched
   const uint64_t j = a.wcnt[(size_t)w * a.G + r] + rank;
   const uint64_t bo = a.wbytes[(size_t)w * a.G + r] + brank;
   uint64_t off[txv_route::kNCols];
-  (void)txv_route::layout(a.tot[2 * r], a.tot[2 * r + 1], a.flags, off);
+  (void)txv_route::layout(tn, a.tot[2 * r + 1], a.flags, off);
   uint8_t* base = a.dst + (size_t)r * a.stride;
   reinterpret_cast<int64_t*>(base + off[txv_route::kHeight])[j] = a.height[i];
   reinterpret_cast<int64_t*>(base + off[txv_route::kSec])[j] = a.ts_sec[i];

@@ -316,7 +316,9 @@ int txv_ctx_fail(txv_ctx* c, int code, const char* msg);
 int route_checked_stage(txv_ctx* c, const txv_votes* v, uint64_t stride);
 int route_checked_consume(txv_ctx* c, PoolDev* dev, uint64_t pool_ticket, uint32_t n);
 int route_checked_launch(txv_ctx* c, const txv_votes* v, const uint8_t* host_st, uint32_t G, void* dst, uint64_t stride,
-                         txv_route_meta* meta);
+                         uint64_t* ticket);
+bool route_checked_args_ok(const txv_votes* v, uint32_t G, const void* dst, uint64_t stride);
+void route_checked_sync_done(txv_ctx* c, uint64_t ticket);
 int submit_checked_stage(txv_ctx* c, const txv_votes* v, uint32_t* slot_out);
 int submit_checked_consume(txv_ctx* c, uint32_t slot, PoolDev* dev, uint64_t pool_ticket, const txv_votes* v);
 int submit_checked_run(txv_ctx* c, uint32_t slot, const txv_votes* v, const uint8_t* host_st, int why, uint64_t* ticket);
@@ -1637,16 +1639,14 @@ int txv_submit_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t p
   return submit_checked_run(ctx, slot, v, why ? nullptr : st.data(), why, ticket);
 }
 
-// txv_route_admitted for the batch a CheckTx ticket is deciding (include/txvote.h): the route
-// kernels read its statuses and signatures in HBM behind the decisions while the batch is in the
-// engine's flight slot, else the ticket's host statuses and the caller's signatures.  Takes the
-// context's route lock, then the pool's, then the context's.
-int txv_route_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t pool_ticket, uint32_t n_shards,
-                      void* dst_dev, uint64_t stride, txv_route_meta* meta_out) {
-  if (!ctx || !v || !p || !pool_ticket || !dst_dev || !meta_out || !n_shards || n_shards > 255) return TXV_EINVAL;
-  if (v->n && (!v->height || !v->txhash || !v->txhash_off || !v->txhash_len || !v->ts_sec || !v->ts_nanos || !v->addr ||
-               !v->addr_len || !v->sig || !v->sig_len))
-    return TXV_EINVAL;
+// txv_route_submit_admitted for the batch a CheckTx ticket is deciding (include/txvote.h): the
+// route kernels read its statuses and signatures in HBM behind the decisions while the batch is in
+// the engine's flight slot (nothing waits for the GPU then), else the ticket's host statuses
+// (finish_ticket: the one case that blocks) and the caller's signatures.  Takes the context's route
+// lock, then the pool's, then the context's; all released when it returns.
+int txv_route_submit_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t pool_ticket, uint32_t n_shards,
+                             void* dst_dev, uint64_t stride, uint64_t* route_ticket) {
+  if (!ctx || !p || !pool_ticket || !route_ticket || !route_checked_args_ok(v, n_shards, dst_dev, stride)) return TXV_EINVAL;
   std::lock_guard<std::mutex> rl(txv_ctx_route_mu(ctx));
   int r;
   if ((r = route_checked_stage(ctx, v, stride))) return r;
@@ -1678,7 +1678,18 @@ int txv_route_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t po
       if (st.size() != v->n) return txv_ctx_fail(ctx, TXV_EINVAL, "txv_route_checked: the batch differs from the pool ticket's");
     }
   }
-  return route_checked_launch(ctx, v, consumed ? nullptr : st.data(), n_shards, dst_dev, stride, meta_out);
+  return route_checked_launch(ctx, v, consumed ? nullptr : st.data(), n_shards, dst_dev, stride, route_ticket);
+}
+
+// submit + wait on the same code
+int txv_route_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t pool_ticket, uint32_t n_shards,
+                      void* dst_dev, uint64_t stride, txv_route_meta* meta_out) {
+  if (!meta_out) return TXV_EINVAL;
+  uint64_t t = 0;
+  if (int r = txv_route_submit_checked(ctx, v, p, pool_ticket, n_shards, dst_dev, stride, &t)) return r;
+  const int r = txv_route_wait(ctx, t, meta_out);
+  route_checked_sync_done(ctx, t);   // the ring idle again: the next synchronous route on the same entry
+  return r;
 }
 
 // the statuses of a submitted batch (tickets in submission order); the engine's event is waited

@@ -25,6 +25,9 @@ namespace txv_route {
 constexpr uint64_t kMagic = 0x3130525654585654ull;   // "TVXTVR01"
 enum Col { kHeight, kSec, kNanos, kOff, kLen, kAddrLen, kSigLen, kAddr, kSig, kTxKey, kNil, kArena, kNCols };
 constexpr uint32_t kFlagTxKey = 0x1u, kFlagNil = 0x2u;   // = TXV_ROUTE_TXKEY / TXV_ROUTE_NIL
+// RouteArgs::tot[2 r] of a shard whose buffer would not fit its stride (the stride guard): the scan
+// writes nothing into its region, the scatter skips its votes, its meta has reserved = 1
+constexpr uint64_t kRefused = ~0ull;
 
 TXV_ROUTE_HD uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 
@@ -63,10 +66,14 @@ struct RouteArgs {
   uint32_t* wcnt;                    // [nw][G] per-wave counts, then their exclusive scan
   uint32_t* wbytes;                  // [nw][G] per-wave TxHash bytes, then their exclusive scan
   uint32_t* maxhl;                   // [G] longest TxHash per shard (zeroed before count)
-  uint64_t* tot;                     // [G][2] votes, arena bytes per shard
+  uint64_t* tot;                     // [G][2] votes (txv_route::kRefused: over its stride), arena bytes per shard
   uint8_t* dst;                      // rank r's buffer at dst + r * stride
   uint64_t stride;
   txv_route_meta* meta;              // [G] mapped host memory
+  // statuses read from the pool engine's flight slot: its sticky look-back error word (HBM) as of
+  // these launches, copied by the scan into mapped host memory beside the metas; null otherwise
+  const uint32_t* pool_err;
+  uint32_t* pool_err_host;
 };
 
 #if defined(__HIPCC__)

@@ -71,8 +71,9 @@ constexpr uint32_t kVcodeEmpty = TXV_VCODE_EMPTY, kVcodeUnknown = TXV_VCODE_UNKN
 constexpr uint32_t kHostValMin = 1u << 18;
 constexpr uint32_t kSignerSlot = 4, kVerifySlot = 5, kIngestSlot = 6;   // signer, verify-only, wire ingest ring (6-8)
 constexpr uint32_t kIngestRing = 3;
-constexpr uint32_t kRouteSlot = kIngestSlot + kIngestRing;   // txv_route_admitted's columns
-constexpr uint32_t kSlots = kRouteSlot + 1;
+constexpr uint32_t kRouteSlot = kIngestSlot + kIngestRing;   // the route ring's columns: entry k in slot kRouteSlot + k
+constexpr uint32_t kRouteRing = TXV_ROUTE_RING;
+constexpr uint32_t kSlots = kRouteSlot + kRouteRing;
 
 struct Slot {
   uint32_t cap = 0, n = 0, n_pad = 0, msg_words = 0, msg_cap_words = 0;
@@ -271,15 +272,27 @@ struct txv_ctx {
   uint32_t n_signers = 0;
   uint32_t *d_sk_scal = nullptr, *d_sk_araw = nullptr, *d_sk_prefix = nullptr, *d_sk_pub = nullptr;
   Slot slots[kSlots];
-  // txv_route_admitted scratch (kernels_route.hip): per-vote shard, per-wave counts / bytes, per
-  // shard longest TxHash and totals, the metas in mapped memory; route_mu serialises route calls
+  // the route ring (txv_route_submit_* / txv_route_wait; kernels_route.hip): ticket t on entry
+  // (t - 1) % kRouteRing with slot kRouteSlot + entry for its columns and its own scratch -- per-vote
+  // shard, per-wave counts / bytes, per shard longest TxHash and totals (not shared: the next
+  // ticket's memset of maxhl would race this ticket's scatter), the metas in mapped memory, the
+  // pool engine's look-back error word as of the decisions it read, the event behind its kernels.
+  // route_mu serialises the submits (never held across a wait); the entries are guarded by mu
+  struct RouteEntry {
+    uint64_t ticket = 0;             // the route in flight on this entry (0 = free)
+    bool waiting = false;            // a txv_route_wait is in its event wait
+    uint32_t G = 0;
+    uint32_t n_cap = 0, w_cap = 0;
+    uint8_t* d_shard = nullptr;
+    uint32_t *d_w = nullptr, *d_max = nullptr;
+    uint64_t* d_tot = nullptr;
+    txv_route_meta *h_meta = nullptr, *m_meta = nullptr;
+    uint32_t *h_perr = nullptr, *m_perr = nullptr;   // mapped: the pool engine's error word, written by the scan
+    const uint32_t* d_perr_src = nullptr;            // the engine's word in HBM (device-sourced statuses), else null
+    hipEvent_t ev = nullptr;
+  } route[kRouteRing];
   std::mutex route_mu;
-  uint32_t route_n_cap = 0, route_w_cap = 0;
-  uint8_t* d_rshard = nullptr;
-  uint32_t *d_rw = nullptr, *d_rmax = nullptr;
-  uint64_t* d_rtot = nullptr;
-  txv_route_meta *h_rmeta = nullptr, *m_rmeta = nullptr;
-  hipEvent_t route_ev = nullptr;
+  uint64_t route_next = 1;           // next route ticket; guarded by mu
   // txv_sig_keys scratch: signatures [n][16] u32, lengths, keys [n][8] u32
   uint32_t pk_cap = 0;
   std::mutex pk_mu;                  // txv_sig_keys' buffers (not c->mu: CheckTx's keys run beside txv_submit_votes)
@@ -1519,6 +1532,8 @@ int txv_init(const txv_config* cfg, txv_ctx** out) {
 void txv_destroy(txv_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
+  for (auto& e : c->route)   // routes still in flight write the caller's buffers and the entries' scratch
+    if (e.ticket && e.ev) (void)hipEventSynchronize(e.ev);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
@@ -1545,8 +1560,10 @@ void txv_destroy(txv_ctx* c) {
   dfree(c->d_arena_seq); dfree(c->d_arena_txkey); dfree(c->d_set_stamp); dfree(c->d_set_blk); dfree(c->d_set_digest); dfree(c->d_bitmap);
   dfree(c->d_set_entry); dfree(c->d_set_txkey); dfree(c->d_tab); dfree(c->d_keys); dfree(c->d_ctr);
   dfree(c->d_addr_slots); dfree(c->d_q);
-  dfree(c->d_rshard); dfree(c->d_rw); dfree(c->d_rmax); dfree(c->d_rtot); hfree(c->h_rmeta);
-  if (c->route_ev) (void)hipEventDestroy(c->route_ev);
+  for (auto& e : c->route) {
+    dfree(e.d_shard); dfree(e.d_w); dfree(e.d_max); dfree(e.d_tot); hfree(e.h_meta); hfree(e.h_perr);
+    if (e.ev) (void)hipEventDestroy(e.ev);
+  }
   for (const auto& rg : c->registered) (void)hipHostUnregister((void*)rg.first);
   dfree(c->d_sk_scal); dfree(c->d_sk_araw); dfree(c->d_sk_prefix); dfree(c->d_sk_pub);
   dfree(c->d_chain); dfree(c->d_chain_sign);
@@ -2508,17 +2525,29 @@ uint32_t route_flags(const txv_votes* v) {
   return (v->txkey ? TXV_ROUTE_TXKEY : 0u) | (v->is_nil ? TXV_ROUTE_NIL : 0u);
 }
 
-// txv_route_admitted's steps (route_mu held by the caller).  Stage: the batch's columns into the
-// route slot (without its signatures when sig_later: txv_route_checked takes them from the pool's
-// flight slot), c->mu held inside.
+// A route submit's steps (route_mu held by the caller: the ticket and its entry are fixed from the
+// stage to the launch).  Stage: the next ticket's entry must be free (TXV_ESTATE, nothing
+// changed); the batch's columns into the entry's slot (without its signatures when sig_later:
+// txv_route_submit_checked takes them from the pool's flight slot), c->mu held inside.
 int route_stage(txv_ctx* c, const txv_votes* v, bool sig_later, uint64_t stride) {
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t k = (uint32_t)((c->route_next - 1) % kRouteRing);
+  txv_ctx::RouteEntry& e = c->route[k];
+  if (e.ticket) { c->err = "four routes already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  int r;
+  if (!e.ev) {   // (the event last: set once the entry's fixed scratch is whole)
+    if ((r = dalloc(c, &e.d_max, 256)) || (r = dalloc(c, &e.d_tot, 512)) ||
+        (r = halloc_mapped(c, &e.h_meta, &e.m_meta, 256)) || (r = halloc_mapped(c, &e.h_perr, &e.m_perr, 1)))
+      return r;
+    HIP_TRY(c, hipEventCreateWithFlags(&e.ev, hipEventDisableTiming));
+  }
+  *e.h_perr = 0;
+  e.d_perr_src = nullptr;   // (route_checked_consume names the pool engine's error word)
   txv_votes w = *v;
   if (sig_later) w.sig = nullptr;
-  int r;
-  if ((r = stage_add(c, kRouteSlot, &w, true))) return r;
-  Slot& s = c->slots[kRouteSlot];
+  if ((r = stage_add(c, kRouteSlot + k, &w, true))) return r;
+  Slot& s = c->slots[kRouteSlot + k];
   const uint64_t need = txv_route_bytes(v->n, s.arena_end, route_flags(v));
   if (stride < need) {
     c->err = "route stride below txv_route_bytes(n, TxHash arena extent, flags) = " + std::to_string(need);
@@ -2529,75 +2558,139 @@ int route_stage(txv_ctx* c, const txv_votes* v, bool sig_later, uint64_t stride)
 
 // Launch: the pool's statuses either given on the host (st: uploaded beside the columns, with the
 // signatures too when they were left out) or already in the slot's pre-check column (st null,
-// dev_status: txv_route_checked), then the three route kernels; waits for the metas.
+// dev_status: route_checked_consume), then the three route kernels on the key stream and the
+// entry's event behind them; hands out the ticket.  Nothing here waits for the GPU.
 int route_launch(txv_ctx* c, const txv_votes* v, const uint8_t* st, bool dev_status, bool sig_later, uint32_t G,
-                 void* dst, uint64_t stride, txv_route_meta* meta) {
+                 void* dst, uint64_t stride, uint64_t* ticket) {
   const uint32_t n = v->n;
   const uint32_t flags = route_flags(v);
   int r;
-  hipEvent_t done;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    HIP_TRY(c, hipSetDevice(c->device));
-    Slot& s = c->slots[kRouteSlot];
-    if (st && n) {   // the pool's statuses beside the columns (the slot's pre-check column is free here)
-      memcpy(s.h_status, st, n);
-      HIP_TRY(c, hipMemcpyAsync(s.d_pre, s.h_status, n, hipMemcpyHostToDevice, c->copy_stream));
-      if (sig_later) {          // the signatures the pool's slot no longer holds, from the caller
-        const bool reg = is_registered(c, v->sig, (uint64_t)n * 64);
-        if (!reg) c->pool->parallel_for(n, [&](uint32_t lo, uint32_t hi) {
-          memcpy(s.h_sigraw + (size_t)lo * 64, v->sig + (size_t)lo * 64, (size_t)(hi - lo) * 64);
-        }, 4096);
-        HIP_TRY(c, hipMemcpyAsync(s.d_sigraw, reg ? (const void*)v->sig : (const void*)s.h_sigraw, (size_t)n * 64,
-                                  hipMemcpyHostToDevice, c->copy_stream));
-      }
-      HIP_TRY(c, hipEventRecord(s.ev[3], c->copy_stream));
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t t = c->route_next;
+  const uint32_t k = (uint32_t)((t - 1) % kRouteRing);
+  txv_ctx::RouteEntry& e = c->route[k];
+  Slot& s = c->slots[kRouteSlot + k];
+  if (st && n) {   // the pool's statuses beside the columns (the slot's pre-check column is free here)
+    memcpy(s.h_status, st, n);
+    HIP_TRY(c, hipMemcpyAsync(s.d_pre, s.h_status, n, hipMemcpyHostToDevice, c->copy_stream));
+    if (sig_later) {          // the signatures the pool's slot no longer holds, from the caller
+      const bool reg = is_registered(c, v->sig, (uint64_t)n * 64);
+      if (!reg) c->pool->parallel_for(n, [&](uint32_t lo, uint32_t hi) {
+        memcpy(s.h_sigraw + (size_t)lo * 64, v->sig + (size_t)lo * 64, (size_t)(hi - lo) * 64);
+      }, 4096);
+      HIP_TRY(c, hipMemcpyAsync(s.d_sigraw, reg ? (const void*)v->sig : (const void*)s.h_sigraw, (size_t)n * 64,
+                                hipMemcpyHostToDevice, c->copy_stream));
     }
-    const uint32_t nw = (n + 63) / 64;
-    if (n > c->route_n_cap) {
-      if ((r = dalloc(c, &c->d_rshard, std::max<uint32_t>(n, 64)))) return r;
-      c->route_n_cap = n;
-    }
-    if ((uint64_t)nw * G > c->route_w_cap) {
-      if ((r = dalloc(c, &c->d_rw, 2 * (size_t)std::max<uint32_t>(nw, 1) * G))) return r;
-      c->route_w_cap = std::max<uint32_t>(nw, 1) * G;
-    }
-    if (!c->d_rmax) {
-      if ((r = dalloc(c, &c->d_rmax, 256)) || (r = dalloc(c, &c->d_rtot, 512)) ||
-          (r = halloc_mapped(c, &c->h_rmeta, &c->m_rmeta, 256)))
-        return r;
-      HIP_TRY(c, hipEventCreateWithFlags(&c->route_ev, hipEventDisableTiming));
-    }
-    RouteArgs a{};
-    a.n = n; a.G = G; a.nw = nw;
-    a.height = s.d_fh; a.ts_sec = s.d_fs; a.ts_nanos = s.d_fn; a.th_off = s.d_fo; a.th_len = s.d_fl; a.th = s.d_arena_th;
-    a.addr = s.d_addr; a.addr_len = s.d_addr_len; a.sig = s.d_sigraw; a.sig_len = s.d_sig_len;
-    a.txkey = s.has_txkey ? s.d_txkey : nullptr;
-    a.nil = s.has_nil ? s.d_nil : nullptr;
-    a.status = (st || dev_status) ? s.d_pre : nullptr;
-    a.flags = flags;
-    a.shard = c->d_rshard; a.wcnt = c->d_rw; a.wbytes = c->d_rw + (size_t)std::max<uint32_t>(nw, 1) * G;
-    a.maxhl = c->d_rmax; a.tot = c->d_rtot;
-    a.dst = static_cast<uint8_t*>(dst); a.stride = stride; a.meta = c->m_rmeta;
-    // on the key stream (CheckTx's engine and the batches' prep run there too): after the uploads
-    HIP_TRY(c, hipStreamWaitEvent(c->key_stream, s.ev[3], 0));
-    HIP_TRY(c, txv_launch_route(&a, c->key_stream));
-    HIP_TRY(c, hipEventRecord(s.ev[4], c->key_stream));   // the slot's next staging waits for it
-    HIP_TRY(c, hipEventRecord(c->route_ev, c->key_stream));
-    s.launched = true;
-    s.staged = false;
-    done = c->route_ev;
+    HIP_TRY(c, hipEventRecord(s.ev[3], c->copy_stream));
   }
-  HIP_TRY(c, hipEventSynchronize(done));
-  memcpy(meta, c->h_rmeta, (size_t)G * sizeof(txv_route_meta));
+  const uint32_t nw = (n + 63) / 64;
+  if (n > e.n_cap || !e.d_shard) {
+    if ((r = dalloc(c, &e.d_shard, std::max<uint32_t>(n, 64)))) return r;
+    e.n_cap = std::max<uint32_t>(n, 64);
+  }
+  if ((uint64_t)std::max<uint32_t>(nw, 1) * G > e.w_cap) {
+    if ((r = dalloc(c, &e.d_w, 2 * (size_t)std::max<uint32_t>(nw, 1) * G))) return r;
+    e.w_cap = std::max<uint32_t>(nw, 1) * G;
+  }
+  RouteArgs a{};
+  a.n = n; a.G = G; a.nw = nw;
+  a.height = s.d_fh; a.ts_sec = s.d_fs; a.ts_nanos = s.d_fn; a.th_off = s.d_fo; a.th_len = s.d_fl; a.th = s.d_arena_th;
+  a.addr = s.d_addr; a.addr_len = s.d_addr_len; a.sig = s.d_sigraw; a.sig_len = s.d_sig_len;
+  a.txkey = s.has_txkey ? s.d_txkey : nullptr;
+  a.nil = s.has_nil ? s.d_nil : nullptr;
+  a.status = (st || dev_status) ? s.d_pre : nullptr;
+  a.flags = flags;
+  a.shard = e.d_shard; a.wcnt = e.d_w; a.wbytes = e.d_w + (size_t)std::max<uint32_t>(nw, 1) * G;
+  a.maxhl = e.d_max; a.tot = e.d_tot;
+  a.dst = static_cast<uint8_t*>(dst); a.stride = stride; a.meta = e.m_meta;
+  a.pool_err = e.d_perr_src; a.pool_err_host = e.m_perr;
+  // on the key stream (CheckTx's engine and the batches' prep run there too): after the uploads
+  HIP_TRY(c, hipStreamWaitEvent(c->key_stream, s.ev[3], 0));
+  HIP_TRY(c, txv_launch_route(&a, c->key_stream));
+  HIP_TRY(c, hipEventRecord(s.ev[4], c->key_stream));   // the slot's next staging waits for it
+  HIP_TRY(c, hipEventRecord(e.ev, c->key_stream));
+  s.launched = true;
+  s.staged = false;
+  e.ticket = t;
+  e.waiting = false;
+  e.G = G;
+  c->route_next = t + 1;
+  *ticket = t;
   return TXV_OK;
 }
 
-int route_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* st, uint32_t G, void* dst, uint64_t stride,
-                   txv_route_meta* meta) {
+// txv_route_wait: the entry's event with no lock held, then its metas; frees the entry
+int route_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta) {
+  txv_ctx::RouteEntry& e = c->route[(ticket - 1) % kRouteRing];
+  hipEvent_t done;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (e.ticket != ticket || e.waiting) { c->err = "txv_route_wait: no such route ticket in flight"; return TXV_ESTATE; }
+    e.waiting = true;
+    done = e.ev;
+  }
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipEventSynchronize(done);
+  std::lock_guard<std::mutex> g(c->mu);
+  const uint32_t G = e.G;
+  e.ticket = 0;
+  e.waiting = false;
+  if (he != hipSuccess) {
+    c->err = std::string("txv_route_wait: ") + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
+  memcpy(meta, e.h_meta, (size_t)G * sizeof(txv_route_meta));
+  if (*(volatile uint32_t*)e.h_perr) {   // the pool's statuses the kernels read are not trusted
+    c->err = "pool engine: look-back scan timed out (device error; the routed votes were chosen by untrusted statuses)";
+    return TXV_EDEVICE;
+  }
+  for (uint32_t r = 0; r < G; ++r)
+    if (meta[r].reserved) {
+      c->err = "route: rank " + std::to_string(r) + " needs " + std::to_string(meta[r].bytes) +
+               " bytes, above the stride (its region is untouched; the other ranks' buffers are valid)";
+      return TXV_ECAPACITY;
+    }
+  return TXV_OK;
+}
+
+// routes still in flight have ended (txv_sync, txv_reset_flow; c->mu held); their tickets stay waitable
+int route_drain(txv_ctx* c) {
+  for (auto& e : c->route)
+    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
+  return TXV_OK;
+}
+
+// A synchronous route (submit + wait in one call) that leaves the ring idle takes its entry again
+// next time: the next ticket is t + kRouteRing, on entry (t - 1) % kRouteRing like t.  A caller
+// that never pipelines then keeps to one entry's slot and scratch (one allocation, warm buffers),
+// as before the ring.  Skipped while a submit is under way (it has read route_next).
+void route_sync_done(txv_ctx* c, uint64_t t) {
+  std::unique_lock<std::mutex> rl(c->route_mu, std::try_to_lock);
+  if (!rl.owns_lock()) return;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->route_next != t + 1) return;
+  for (const auto& e : c->route)
+    if (e.ticket) return;
+  c->route_next = t + kRouteRing;
+}
+
+int route_submit_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* st, uint32_t G, void* dst, uint64_t stride,
+                          uint64_t* ticket) {
+  std::lock_guard<std::mutex> g(c->route_mu);
   int r;
   if ((r = route_stage(c, v, false, stride))) return r;
-  return route_launch(c, v, st, false, false, G, dst, stride, meta);
+  return route_launch(c, v, st, false, false, G, dst, stride, ticket);
+}
+
+// what every route entry point checks before it takes a lock: the columns, the shard count, and the
+// 16-byte alignment the kernels' vector stores at dst + r * stride + column offset need
+bool route_args_ok(const txv_votes* v, uint32_t G, const void* dst, uint64_t stride, bool dst_aligned) {
+  if (!v || !dst || !G || G > 255) return false;
+  if (v->n && (!v->height || !v->txhash || !v->txhash_off || !v->txhash_len || !v->ts_sec || !v->ts_nanos || !v->addr ||
+               !v->addr_len || !v->sig || !v->sig_len))
+    return false;
+  return stride % 16 == 0 && (!dst_aligned || (uintptr_t)dst % 16 == 0);
 }
 
 // the receiving rank: a route buffer (on this context's device) into AddVote slot `slot`, by
@@ -2664,6 +2757,16 @@ int route_pack_host(const txv_votes* v, const uint8_t* st, uint32_t G, uint8_t* 
     mx[r] = std::max(mx[r], len);
   }
   if (stride < txv_route_bytes(n, ae, flags)) return TXV_EINVAL;
+  // the stride guard (kernels_route.hip txv_k_route_scan's rule), before a byte is written: a rank
+  // holds the sum of its votes' TxHash lengths, above the extent when votes share offsets
+  bool refused = false;
+  for (uint32_t r = 0; r < G; ++r) {
+    uint64_t off[txv_route::kNCols];
+    const uint64_t total = txv_route::layout(cnt[r], ab[r], flags, off);
+    meta[r] = txv_route_meta{cnt[r], mx[r], flags, total > stride ? 1u : 0u, ab[r], total};
+    refused |= total > stride;
+  }
+  if (refused) return TXV_ECAPACITY;
   std::vector<uint64_t> pos(G, 0), bpos(G, 0);
   for (uint32_t r = 0; r < G; ++r) {
     uint64_t off[txv_route::kNCols];
@@ -2672,7 +2775,6 @@ int route_pack_host(const txv_votes* v, const uint8_t* st, uint32_t G, uint8_t* 
     memset(b, 0, total);
     const uint64_t hdr[8] = {txv_route::kMagic, cnt[r], ab[r], flags, mx[r], total, 0, 0};
     memcpy(b, hdr, 64);
-    meta[r] = txv_route_meta{cnt[r], mx[r], flags, 0, ab[r], total};
   }
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t r = shard[i];
@@ -2712,20 +2814,28 @@ uint64_t txv_route_bytes(uint32_t n, uint64_t arena_bytes, uint32_t flags) {
 
 int txv_route_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* pool_status, uint32_t n_shards, void* dst_dev,
                        uint64_t stride, txv_route_meta* meta_out) {
-  if (!c || !v || !dst_dev || !meta_out || !n_shards || n_shards > 255) return TXV_EINVAL;
-  if (v->n && (!v->height || !v->txhash || !v->txhash_off || !v->txhash_len || !v->ts_sec || !v->ts_nanos || !v->addr ||
-               !v->addr_len || !v->sig || !v->sig_len))
-    return TXV_EINVAL;
-  std::lock_guard<std::mutex> g(c->route_mu);
-  return route_admitted(c, v, pool_status, n_shards, dst_dev, stride, meta_out);
+  if (!c || !meta_out || !route_args_ok(v, n_shards, dst_dev, stride, true)) return TXV_EINVAL;
+  uint64_t t = 0;
+  if (int r = route_submit_admitted(c, v, pool_status, n_shards, dst_dev, stride, &t)) return r;
+  const int r = route_wait(c, t, meta_out);
+  route_sync_done(c, t);
+  return r;
+}
+
+int txv_route_submit_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* pool_status, uint32_t n_shards,
+                              void* dst_dev, uint64_t stride, uint64_t* route_ticket) {
+  if (!c || !route_ticket || !route_args_ok(v, n_shards, dst_dev, stride, true)) return TXV_EINVAL;
+  return route_submit_admitted(c, v, pool_status, n_shards, dst_dev, stride, route_ticket);
+}
+
+int txv_route_wait(txv_ctx* c, uint64_t route_ticket, txv_route_meta* meta_out) {
+  if (!c || !route_ticket || !meta_out) return TXV_EINVAL;
+  return route_wait(c, route_ticket, meta_out);
 }
 
 int txv_route_pack_host(const txv_votes* v, const uint8_t* pool_status, uint32_t n_shards, void* dst, uint64_t stride,
                         txv_route_meta* meta_out) {
-  if (!v || !dst || !meta_out || !n_shards || n_shards > 255) return TXV_EINVAL;
-  if (v->n && (!v->height || !v->txhash || !v->txhash_off || !v->txhash_len || !v->ts_sec || !v->ts_nanos || !v->addr ||
-               !v->addr_len || !v->sig || !v->sig_len))
-    return TXV_EINVAL;
+  if (!meta_out || !route_args_ok(v, n_shards, dst, stride, false)) return TXV_EINVAL;
   return route_pack_host(v, pool_status, n_shards, static_cast<uint8_t*>(dst), stride, meta_out);
 }
 
@@ -2757,7 +2867,8 @@ int txv_route_view(const void* buf, uint64_t bytes, txv_votes* out) {
 
 int txv_submit_routed(txv_ctx* c, const void* buf_dev, const txv_route_meta* meta, uint64_t* ticket) {
   if (!c || !buf_dev || !meta || !ticket) return TXV_EINVAL;
-  std::lock_guard<std::mutex> g(c->mu);
+  std::lock_guard<std::mutex> so(c->sub_mu);   // one submit at a time, as txv_submit_votes: a route wait on
+  std::lock_guard<std::mutex> g(c->mu);        // one thread beside a routed submit on another is the normal pattern
   HIP_TRY(c, hipSetDevice(c->device));
   const uint64_t t = c->next_ticket;
   const uint32_t slot = (uint32_t)((t - 1) % kSubmitRing);
@@ -2987,6 +3098,7 @@ int txv_reset_flow(txv_ctx* c) {
   if (!c) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
+  if (int r = route_drain(c)) return r;
   if (!c->n_vals) return TXV_OK;
   return reset_tally(c, false);
 }
@@ -2995,6 +3107,11 @@ void* txv_flow_stream(txv_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int txv_sync(txv_ctx* c) {
   if (!c) return TXV_EINVAL;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = route_drain(c)) return r;
+  }
   HIP_TRY(c, hipStreamSynchronize(c->vstream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return TXV_OK;
@@ -4565,20 +4682,30 @@ int route_checked_consume(txv_ctx* c, PoolDev* dev, uint64_t pool_ticket, uint32
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!n) return TXV_OK;
-  Slot& s = c->slots[kRouteSlot];
+  const uint32_t k = (uint32_t)((c->route_next - 1) % kRouteRing);   // the entry route_checked_stage staged
+  Slot& s = c->slots[kRouteSlot + k];
   hipStream_t ks = c->key_stream;
   HIP_TRY(c, hipStreamWaitEvent(ks, s.ev[3], 0));
   const int r = pooldev_consume(c, dev, pool_ticket, n, ks, s.d_sigraw, s.d_pre, false, true);
   if (r) return r;
+  // the engine's sticky look-back error word as of these decisions (pooldev_finish's check, which
+  // the caller's txv_pool_check_wait may make only after the buffers were shipped): txv_route_wait
+  // returns TXV_EDEVICE when it is set.  The scan kernel copies the word (no copy command of its own
+  // on the stream: the route's kernels run behind these reads, so behind the decisions)
+  c->route[k].d_perr_src = dev->d_err;
   HIP_TRY(c, hipEventRecord(s.ev[3], ks));
   return TXV_OK;
 }
 
 std::mutex& txv_ctx_route_mu(txv_ctx* c) { return c->route_mu; }
+bool route_checked_args_ok(const txv_votes* v, uint32_t G, const void* dst, uint64_t stride) {
+  return route_args_ok(v, G, dst, stride, true);
+}
+void route_checked_sync_done(txv_ctx* c, uint64_t ticket) { route_sync_done(c, ticket); }
 int route_checked_stage(txv_ctx* c, const txv_votes* v, uint64_t stride) { return route_stage(c, v, true, stride); }
 int route_checked_launch(txv_ctx* c, const txv_votes* v, const uint8_t* host_st, uint32_t G, void* dst, uint64_t stride,
-                         txv_route_meta* meta) {
-  return route_launch(c, v, host_st, host_st == nullptr, true, G, dst, stride, meta);
+                         uint64_t* ticket) {
+  return route_launch(c, v, host_st, host_st == nullptr, true, G, dst, stride, ticket);
 }
 int txv_ctx_fail(txv_ctx* c, int code, const char* msg) {
   std::lock_guard<std::mutex> g(c->mu);

@@ -66,6 +66,17 @@ class UpdateListError(TxvInfraError):
         self.n = n
 
 
+class TxvCapacityError(TxvInfraError):
+    """Context.route_wait / route_admitted / route_checked: a rank's buffer would not fit its stride
+    (TXV_ECAPACITY).  metas = every rank's txv_route_meta: the refused ones have reserved = 1, their
+    regions untouched and bytes = the stride they need; the other ranks' buffers are valid."""
+
+    def __init__(self, what, msg, metas):
+        super().__init__(f"{what} failed ({E_CAPACITY}): {msg}")
+        self.rc = E_CAPACITY
+        self.metas = metas
+
+
 class _Cfg(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("max_batch", ctypes.c_uint32), ("max_txs", ctypes.c_uint32),
                 ("max_validators", ctypes.c_uint32), ("max_accepted", ctypes.c_uint32),
@@ -100,6 +111,7 @@ EVENT_DTYPE = np.dtype([("vote_index", "<u4"), ("tx_index", "<u4"), ("sum", "<i8
 ROUTE_META_DTYPE = np.dtype([("n", "<u4"), ("max_txhash_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4"),
                              ("arena_bytes", "<u8"), ("bytes", "<u8")])
 ROUTE_TXKEY, ROUTE_NIL = 0x1, 0x2
+ROUTE_RING = 4   # TXV_ROUTE_RING: route tickets in flight per context
 
 
 _lib = None
@@ -208,6 +220,11 @@ def lib():
             "txv_route_admitted": ([vp, ctypes.POINTER(_Votes), vp, u32, vp, ctypes.c_uint64, vp], ctypes.c_int),
             "txv_route_checked": ([vp, ctypes.POINTER(_Votes), vp, ctypes.c_uint64, u32, vp, ctypes.c_uint64, vp],
                                   ctypes.c_int),
+            "txv_route_submit_admitted": ([vp, ctypes.POINTER(_Votes), vp, u32, vp, ctypes.c_uint64,
+                                           ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_route_submit_checked": ([vp, ctypes.POINTER(_Votes), vp, ctypes.c_uint64, u32, vp, ctypes.c_uint64,
+                                          ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_route_wait": ([vp, ctypes.c_uint64, vp], ctypes.c_int),
             "txv_route_pack_host": ([ctypes.POINTER(_Votes), vp, u32, vp, ctypes.c_uint64, vp], ctypes.c_int),
             "txv_route_view": ([vp, ctypes.c_uint64, ctypes.POINTER(_Votes)], ctypes.c_int),
             "txv_submit_routed": ([vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
@@ -241,7 +258,8 @@ EXPORTED_SYMBOLS = [
     "txv_commit_state_unpack", "txv_set_commit_sink", "txv_slot_kernel_ms", "txv_slot_verify_ms", "txv_flow_stream",
     "txv_ingest_msgs", "txv_ingest_submit", "txv_ingest_wait", "txv_pool_prepare",
     "txv_ingest_decode", "txv_ingest_admit", "txv_route_bytes", "txv_route_admitted", "txv_route_checked", "txv_route_pack_host",
-    "txv_route_view", "txv_submit_routed", "txv_ingest_admit_submit", "txv_ingest_admit_finish",
+    "txv_route_view", "txv_submit_routed", "txv_route_submit_admitted", "txv_route_submit_checked", "txv_route_wait",
+    "txv_ingest_admit_submit", "txv_ingest_admit_finish",
     "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired"]
 
 
@@ -357,11 +375,15 @@ def route_flags(batch: VoteBatch) -> int:
 
 
 def route_stride(batch: VoteBatch) -> int:
-    """bytes every rank's route buffer needs for this batch whatever the split
-    (txv_route_bytes of all n votes and the whole TxHash arena extent)"""
+    """bytes every rank's route buffer needs for this batch whatever the split: txv_route_bytes of
+    all n votes and of max(TxHash arena extent, sum of the non-nil votes' TxHash lengths).  A rank's
+    buffer holds the sum of its votes' TxHash lengths, which exceeds the extent when votes share
+    TxHash offsets (StreamWorkload / SyntheticWorkload batches); the extent is what the route calls
+    require at least."""
     live = np.ones(batch.n, bool) if batch.is_nil is None else batch.is_nil == 0
     ext = int((batch.txhash_off[live].astype(np.int64) + batch.txhash_len[live]).max()) if live.any() else 0
-    return int(lib().txv_route_bytes(batch.n, ext, route_flags(batch)))
+    total = int(batch.txhash_len[live].sum(dtype=np.int64))
+    return int(lib().txv_route_bytes(batch.n, max(ext, total), route_flags(batch)))
 
 
 def route_pack_host(batch: VoteBatch, pool_status=None, n_shards: int = 1):
@@ -619,17 +641,54 @@ class Context:
         meta = np.zeros(n_shards, ROUTE_META_DTYPE)
         st = None if pool_status is None else np.ascontiguousarray(pool_status, np.uint8)
         vs = batch.c_struct()
-        self._chk(lib().txv_route_admitted(self._h, ctypes.byref(vs), None if st is None else st.ctypes.data, n_shards,
-                                           ctypes.c_void_p(dst_ptr), stride, meta.ctypes.data), "txv_route_admitted")
+        self._chk_route(lib().txv_route_admitted(self._h, ctypes.byref(vs), None if st is None else st.ctypes.data,
+                                                 n_shards, ctypes.c_void_p(dst_ptr), stride, meta.ctypes.data),
+                        "txv_route_admitted", meta)
         return meta
+
+    def _chk_route(self, rc: int, what: str, meta):
+        if rc == E_CAPACITY:
+            raise TxvCapacityError(what, lib().txv_last_error(self._h).decode(), meta)
+        return self._chk(rc, what)
+
+    def route_submit_admitted(self, batch: VoteBatch, pool_status, n_shards: int, dst_ptr: int, stride: int) -> int:
+        """txv_route_submit_admitted: route_admitted's first half; returns a route ticket for
+        route_wait without waiting for the GPU.  Up to ROUTE_RING tickets in flight (TXV_ESTATE
+        beyond), their destination regions apart; the batch's arrays may be reused on return."""
+        st = None if pool_status is None else np.ascontiguousarray(pool_status, np.uint8)
+        vs = batch.c_struct()
+        t = ctypes.c_uint64()
+        self._chk(lib().txv_route_submit_admitted(self._h, ctypes.byref(vs), None if st is None else st.ctypes.data,
+                                                  n_shards, ctypes.c_void_p(dst_ptr), stride, ctypes.byref(t)),
+                  "txv_route_submit_admitted")
+        return t.value
+
+    def route_submit_checked(self, batch: VoteBatch, pool, pool_ticket: int, n_shards: int, dst_ptr: int,
+                             stride: int) -> int:
+        """txv_route_submit_checked: route_checked's first half; while the CheckTx batch is in the
+        pool engine's flight slot nothing here waits for the GPU.  Returns a route ticket."""
+        vs = batch.c_struct()
+        t = ctypes.c_uint64()
+        self._chk(lib().txv_route_submit_checked(self._h, ctypes.byref(vs), pool._h, pool_ticket, n_shards,
+                                                 ctypes.c_void_p(dst_ptr), stride, ctypes.byref(t)),
+                  "txv_route_submit_checked")
+        return t.value
+
+    def route_wait(self, ticket: int, n_shards: int) -> np.ndarray:
+        """txv_route_wait: the ticket's metas once its buffers are written (n_shards as submitted).
+        TxvCapacityError (carrying the metas) when a rank was refused."""
+        meta = np.zeros(255, ROUTE_META_DTYPE)   # the call writes as many as were submitted (<= 255)
+        self._chk_route(lib().txv_route_wait(self._h, ticket, meta.ctypes.data), "txv_route_wait", meta[:n_shards])
+        return meta[:n_shards]
 
     def route_checked(self, batch: VoteBatch, pool, pool_ticket: int, n_shards: int, dst_ptr: int, stride: int) -> np.ndarray:
         """txv_route_checked: route_admitted for the batch TxVotePool.check_submit(batch) returned
         pool_ticket for, its statuses and signatures read in HBM behind the pool's decisions"""
         meta = np.zeros(n_shards, ROUTE_META_DTYPE)
         vs = batch.c_struct()
-        self._chk(lib().txv_route_checked(self._h, ctypes.byref(vs), pool._h, pool_ticket, n_shards,
-                                          ctypes.c_void_p(dst_ptr), stride, meta.ctypes.data), "txv_route_checked")
+        self._chk_route(lib().txv_route_checked(self._h, ctypes.byref(vs), pool._h, pool_ticket, n_shards,
+                                                ctypes.c_void_p(dst_ptr), stride, meta.ctypes.data),
+                        "txv_route_checked", meta)
         return meta
 
     def submit_routed(self, buf_ptr: int, meta) -> int:

@@ -14,7 +14,9 @@ order-dependent LRU keyed by SHA-256(Signature) with one Size cap, so CheckTx ca
 shard without changing which votes it admits.  It runs on one owner rank (the node's reactor
 process); the votes it admits are packed per rank on the owner's GPU by the C-ABI's
 txv_route_admitted (kernels_route.hip: shard, arrival-order rank and TxHash arena offset of every
-admitted vote, each rank's columns written into its own buffer) -- or on the host by
+admitted vote, each rank's columns written into its own buffer; pipelined as
+txv_route_submit_checked / txv_route_wait, Context.route_submit_checked / route_wait: up to four
+batches' routes in flight behind their CheckTx, each into its own buffers) -- or on the host by
 txv_route_pack_host -- sent buffer r to rank r (scatter_routed: one meta broadcast + point-to-point
 sends, RCCL over xGMI), and each rank runs its TxFlow chain straight from the received buffer in
 its HBM (Context.submit_routed): the path's one real data exchange besides the commit-state

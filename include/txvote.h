@@ -356,7 +356,16 @@ int txv_commit_state_unpack(const void* src, uint32_t n_sets_cap, uint32_t* n_se
  * TXV_POOL_OK; pool_status NULL = all) into the buffer of its rank r at dst_dev + r * stride, in
  * arrival order, and returns each rank's txv_route_meta (the header's values: the receiving rank
  * needs n, max_txhash_len and the byte count before it receives); synchronous (dst_dev is written
- * when it returns).  stride >= txv_route_bytes(votes->n, TxHash arena extent, flags).  The
+ * when it returns).
+ * Sizes: dst_dev and stride are multiples of 16 (the kernels store 16 bytes at a time at dst_dev +
+ * r * stride + a column offset; TXV_EINVAL otherwise, from every route call), and stride >=
+ * txv_route_bytes(votes->n, TxHash arena extent, flags) (TXV_EINVAL below that).  A rank's buffer
+ * holds the sum of its votes' TxHash lengths, which exceeds the extent when votes share TxHash
+ * offsets: a rank whose buffer would not fit its stride is refused -- nothing is written into its
+ * region, its meta carries the true n, arena_bytes and bytes (the size it needs) with reserved = 1,
+ * and the call returns TXV_ECAPACITY; the other ranks' buffers are complete and valid.  A stride
+ * of txv_route_bytes(n, max(extent, sum of the non-nil votes' TxHash lengths), flags) fits every
+ * split.  The
  * node's collective then sends buffer r to rank r as it is (RCCL over xGMI: no host copy), and
  * rank r runs its TxFlow chain straight from it: txv_submit_routed (a txv_submit_votes ticket,
  * collected by txv_wait_votes; the buffer may be reused once the call returns).  Buffer layout
@@ -371,7 +380,7 @@ typedef struct {
   uint32_t n;                /* votes routed to the rank */
   uint32_t max_txhash_len;   /* their longest TxHash (the receiver's SignBytes bound) */
   uint32_t flags;            /* TXV_ROUTE_* */
-  uint32_t reserved;
+  uint32_t reserved;         /* 1: the rank was refused (bytes > stride), its region untouched */
   uint64_t arena_bytes;      /* TxHash bytes */
   uint64_t bytes;            /* the buffer's size (txv_route_bytes) */
 } txv_route_meta;
@@ -386,6 +395,37 @@ int txv_route_admitted(txv_ctx* ctx, const txv_votes* votes, const uint8_t* pool
  * pool ticket is still the caller's to wait.  Takes the route lock, the pool's, the context's. */
 int txv_route_checked(txv_ctx* ctx, const txv_votes* votes, struct txv_pool* pool, uint64_t pool_ticket, uint32_t n_shards,
                       void* dst_dev, uint64_t stride, txv_route_meta* meta_out);
+/* The route as a submit / wait pair (the hop reactor.go:170-190 -> txvotepool.go:187-261 ->
+ * service.go:123-166 pipelined like its neighbours txv_pool_check_submit / txv_submit_checked):
+ * up to TXV_ROUTE_RING routes in flight per context, ticket t on ring entry (t - 1) %
+ * TXV_ROUTE_RING, each entry with its own staging buffers and scratch.  A submit whose entry
+ * still holds an unwaited ticket returns TXV_ESTATE and changes nothing; waits may come in any
+ * order.  The route kernels of consecutive tickets run in submission order; the route lock is held
+ * for the submit only, never across a wait.
+ * txv_route_submit_admitted: txv_route_admitted's first half (the columns and pool_status staged
+ * and uploaded, the kernels enqueued); returns without waiting for the GPU.
+ * txv_route_submit_checked: txv_route_checked's first half.  While the CheckTx batch is in the
+ * pool engine's flight slot the call waits for nothing on the GPU: the columns go through the
+ * entry's pinned buffers on the copy stream, the statuses and signatures come from the flight
+ * slot on the key stream behind the decisions, the kernels run behind them.  Only a pool ticket no
+ * longer in the engine can block: its statuses are taken on the host, which may finish earlier
+ * pool tickets first.
+ * txv_route_wait: waits for the ticket's kernels with no lock held, copies its n_shards metas to
+ * meta_out and frees the entry; dst_dev is written when it returns.  TXV_ECAPACITY: a rank was
+ * refused (meta.reserved = 1; see Sizes above), the other ranks' buffers are valid.  TXV_EDEVICE:
+ * the pool engine's look-back error word was set behind the decisions the route read (the
+ * statuses are not trusted: ship nothing).  TXV_ESTATE: no such ticket in flight.
+ * The caller keeps the destination regions of in-flight tickets apart.  Host columns may be reused
+ * once the submit returns; memory registered with txv_host_register is read until the wait (the
+ * rule of txv_pool_check_submit).  txv_route_admitted / txv_route_checked are submit + wait on the
+ * same code (TXV_ESTATE too when four tickets are unwaited); one that leaves the ring idle skips
+ * to the next ticket of its own entry, so a caller that never pipelines uses one entry.  txv_sync, txv_reset_flow and txv_destroy wait for the routes in flight first. */
+#define TXV_ROUTE_RING 4
+int txv_route_submit_admitted(txv_ctx* ctx, const txv_votes* votes, const uint8_t* pool_status, uint32_t n_shards,
+                              void* dst_dev, uint64_t stride, uint64_t* route_ticket);
+int txv_route_submit_checked(txv_ctx* ctx, const txv_votes* votes, struct txv_pool* pool, uint64_t pool_ticket,
+                             uint32_t n_shards, void* dst_dev, uint64_t stride, uint64_t* route_ticket);
+int txv_route_wait(txv_ctx* ctx, uint64_t route_ticket, txv_route_meta* meta_out);
 int txv_route_pack_host(const txv_votes* votes, const uint8_t* pool_status, uint32_t n_shards, void* dst,
                         uint64_t stride, txv_route_meta* meta_out);
 int txv_route_view(const void* buf, uint64_t bytes, txv_votes* out);
