@@ -1259,6 +1259,13 @@ __global__ void __launch_bounds__(64) txv_k_sign(SignArgs a) {
 
 // ---------------------------------------------------------------- field self-test
 // op 0: a*b  1: a^2  2: a+b  3: a-b  4: canon(a)  5: invert(a)  6: sc_reduce512(a||b)
+// 7: fe_invert_var(a) (K1c's inversion, canonical)
+// 8..10: the walk's radix-2^25.5 multiplies at their documented operand bounds, with
+//        x10 = fe10_strict(fe10_from_fe(a)), y10 likewise of b, multiples built by fe10_add
+//        (a = b = 2^255 - 1 puts every limb of 4 x10 / 3 y10 at 4 (2^w - 1) / 3 (2^w - 1)):
+//        8: fe10_mul(4 x10, 3 y10)   9, 10: first / second product of
+//        fe10_mul2(4 x10, 3 y10, 3 y10, 3 x10); each through fe_from_fe10
+// (txv_fe_selftest refuses any other op with TXV_EINVAL)
 __global__ void txv_k_fe_selftest(const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t n, int op) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1273,6 +1280,23 @@ __global__ void txv_k_fe_selftest(const uint32_t* a, const uint32_t* b, uint32_t
     case 3: r = fe_sub(x, y); break;
     case 4: r = fe_canon(x); break;
     case 5: r = fe_invert(x); break;
+    case 7: r = fe_invert_var(x); break;
+    case 8:
+    case 9:
+    case 10: {
+      const fe10 x1 = fe10_strict(fe10_from_fe(x)), y1 = fe10_strict(fe10_from_fe(y));
+      const fe10 x2 = fe10_add(x1, x1), x3 = fe10_add(x2, x1), x4 = fe10_add(x2, x2);
+      const fe10 y3 = fe10_add(fe10_add(y1, y1), y1);
+      fe10 h1, h2;
+      if (op == 8) {
+        h1 = fe10_mul(x4, y3);
+        h2 = h1;
+      } else {
+        fe10_mul2(x4, y3, y3, x3, h1, h2);
+      }
+      r = fe_from_fe10(op == 10 ? h2 : h1);
+      break;
+    }
     default: {
       uint32_t t[16];
 #pragma unroll
@@ -1501,6 +1525,7 @@ hipError_t txv_launch_sign(const SignArgs* args, hipStream_t st) {
 
 hipError_t txv_launch_fe_selftest(const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t n, int op,
                                   hipStream_t st) {
+  if (op < 0 || op > 10) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(txv_k_fe_selftest, dim3((n + 63) / 64), dim3(64), 0, st, a, b, out, n, op);
   return hipGetLastError();

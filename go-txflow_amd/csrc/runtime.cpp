@@ -3178,7 +3178,7 @@ int64_t txv_staged_bytes(txv_ctx* c) { return c ? (int64_t)c->staged_bytes : TXV
 int txv_base_window(txv_ctx* c) { return c ? c->b_w : TXV_EINVAL; }
 
 int txv_fe_selftest(txv_ctx* c, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t n, int op) {
-  if (!c || !a || !b || !out) return TXV_EINVAL;
+  if (!c || !a || !b || !out || op < 0 || op > 10) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   uint32_t *da = nullptr, *db = nullptr, *dout = nullptr;

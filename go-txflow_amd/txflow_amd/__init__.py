@@ -972,7 +972,12 @@ class Context:
         return d
 
     def fe_selftest(self, a: np.ndarray, b: np.ndarray, op: int) -> np.ndarray:
+        """txv_fe_selftest on [n, 8] u32 words: op 0..6 radix-2^32 field ops and sc_reduce512,
+        7 fe_invert_var, 8 fe10_mul and 9 / 10 the halves of fe10_mul2 at their operand bounds
+        (include/txvote.h); any other op raises TxvInfraError (TXV_EINVAL)"""
         a = np.ascontiguousarray(a, dtype=np.uint32); b = np.ascontiguousarray(b, dtype=np.uint32)
+        if a.shape != b.shape or a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("fe_selftest: a and b must both be [n, 8]")
         n = a.shape[0]
         out = np.zeros((n, 8), np.uint32)
         self._chk(lib().txv_fe_selftest(self._h, a.ctypes.data, b.ctypes.data, out.ctypes.data, n, op), "selftest")

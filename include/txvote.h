@@ -713,7 +713,14 @@ int txv_ingest_admit_finish(txv_ctx* ctx, uint64_t ticket, uint8_t* wire_status,
 int txv_ingest_wait(txv_ctx* ctx, uint64_t ticket, uint8_t* flow_status, txv_commit_event* ev_out, uint32_t ev_cap,
                     uint32_t* n_ev);
 
-/* ---- self-test hook: field/scalar ops on device (tests only) ---- */
+/* ---- self-test hook: field/scalar ops on device (tests only) ----
+ * a, b, out: n x 8 little-endian u32 words.  op:
+ *   0 a*b   1 a^2   2 a+b   3 a-b   (radix-2^32 fe, weakly reduced results)
+ *   4 canon(a)   5 fe_invert(a)   6 sc_reduce512(a || b)   7 fe_invert_var(a) (canonical)
+ *   8 fe_from_fe10(fe10_mul(4 x10, 3 y10)) with x10 = fe10_strict(fe10_from_fe(a)), y10 of b, the
+ *     multiples built by fe10_add: the walk's multiply at its documented operand bounds
+ *   9, 10 the first / second product of fe10_mul2(4 x10, 3 y10, 3 y10, 3 x10), likewise
+ * Any other op: TXV_EINVAL. */
 int txv_fe_selftest(txv_ctx* ctx, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t n, int op);
 
 #ifdef __cplusplus

@@ -12,7 +12,9 @@ checked on a slice of every batch through txv_verify_batch.
 Mix per batch (fractions of all votes; Appendix C): 10% bad = R bit-flip 2%, S bit-flip 2%,
 signed field changed after signing 2% (Height, Timestamp or TxHash), s+L 1%, s top-3 bits 0.5%,
 sig length != 64 0.5%, unknown validator 0.5%, empty address 0.25%, nil 0.1%; crafted-key votes 2%
-(of which non-canonical R encodings of the identity 0.5%); 5% exact replays and 5% conflicting
+(of which 0.5% the non-canonical-R class: mixed-order keys, s = k a, so that R' lands exactly on a
+small-order point after a generic walk, named by R canonically in one vote of four and
+non-canonically in the rest -- C4Stream._small_order_vote); 5% exact replays and 5% conflicting
 re-signed votes (same validator + tx, new timestamp), sourced from this batch or the previous one
 (cross-batch state).  Crafted validators: identity (canonical, y+p, x=0 with sign bit), order 2,
 order 4 (both roots, y+p encoding), order 8, mixed-order A+T4 / A+T8, and an undecodable key.
@@ -109,6 +111,17 @@ class C4Stream:
         self.seeds = validator_seeds(n_honest)
         honest = ctx.keygen(self.seeds)
         self.crafted = crafted_keys()
+        # the non-canonical-R class (_small_order_vote) signs with the mixed-order keys A = [a]B + T:
+        # crafted index -> [-[j]T for j in 0..7], T = A - [a]B; and the 14 encodings of E[8]
+        self.nc_neg_t = {}
+        for vi, (name, pub, a) in enumerate(self.crafted):
+            if name in ("mixed4", "mixed8"):
+                y = int.from_bytes(pub, "little")
+                A = (E.recover_x(y & ((1 << 255) - 1), y >> 255), y & ((1 << 255) - 1))
+                self.nc_neg_t[vi] = E.neg_multiples(E.add(A, E.neg(E.mul(a, E.B))))
+        encs = E.torsion_encodings()
+        self.nc_canon = [e for e in encs if e[3]]
+        self.nc_noncanon = [e for e in encs if not e[3]]
         self.pubs = honest + [k[1] for k in self.crafted]
         self.n_vals = len(self.pubs)
         self.powers = np.ones(self.n_vals, np.int64)
@@ -162,6 +175,38 @@ class C4Stream:
         s = (r + k * (a or 0)) % E.L
         return R + s.to_bytes(32, "little")
 
+    def _small_order_vote(self, f, i: int, primary: bool):
+        """Signature of vote i of the non-canonical-R class: a mixed-order key A = [a]B + T, R one
+        of the 14 encodings of a point Q of E[8] and s = k a, so that R' = [s]B - [k]A = -[k mod 8]T
+        is exactly Q after a walk with generic digits (ed_math.rprime_sig).  One vote in four
+        targets a canonical encoding (valid: ADDED), the others a non-canonical one, which only
+        an encoder that canonicalises R' rejects (ErrVoteInvalidSignature); the encodings are tried
+        in a drawn order.  s differs per message, so CheckTx (keyed by SHA-256(Signature)) keeps
+        every vote.  When this message's k lands on no encoding of the target kind, a primary
+        redraws its tx (random for this class anyway) and a conflict copy, whose tx and validator
+        are its source's, steps ts_nanos within [1, 999 999 999]; each attempt succeeds with
+        probability >= 1/2."""
+        import txflow_amd as T
+        rng = self.rng
+        vi = int(f["val"][i]) - self.n_honest
+        _, pub, a = self.crafted[vi]
+        encs = self.nc_canon if rng.random() < 0.25 else self.nc_noncanon
+        for _ in range(64):
+            msg = T.sign_bytes(int(f["height"][i]), self.hashes[f["tx"][i]].tobytes(), 1_700_000_000,
+                               int(f["ts_nanos"][i]), CHAIN)
+            for e in rng.permutation(len(encs)):
+                _, rb, q, _ = encs[e]
+                sig = E.rprime_sig(pub, a, self.nc_neg_t[vi], rb, q, msg)
+                if sig is not None:
+                    f["sig"][i] = np.frombuffer(sig, np.uint8)
+                    return
+            if primary:
+                f["tx"][i] = rng.integers(0, self.epoch_txs)
+                f["txoff"][i] = np.uint32(int(f["tx"][i]) * 64)
+            else:
+                f["ts_nanos"][i] = int(f["ts_nanos"][i]) % 999_999_999 + 1
+        raise AssertionError("non-canonical-R vote: no encoding matched in 64 attempts")
+
     def next_batch(self):
         # epochs by batches generated (a pipelined driver generates batch k+1 before checking k)
         if self.epoch < 0 or (self.generated % self.bpe) == 0:
@@ -175,7 +220,7 @@ class C4Stream:
         n_base = n - n_rep - n_conf - n_craft - n_nc - n_unknown - n_empty - n_nil
         n_base = min(n_base, len(self.pairs) - self.pair_pos)
         n_prim = n_base + n_craft + n_nc + n_unknown + n_empty + n_nil
-        # primary votes: base (honest pairs), crafted, non-canonical-R identity, unknown, empty, nil
+        # primary votes: base (honest pairs), crafted, non-canonical-R (small-order R'), unknown, empty, nil
         tx = np.empty(n_prim, np.int64)
         val = np.empty(n_prim, np.int64)
         pr = self.pairs[self.pair_pos:self.pair_pos + n_base]
@@ -186,8 +231,7 @@ class C4Stream:
         n_cr = len(self.crafted)
         val[o:o + n_craft] = self.n_honest + rng.integers(0, n_cr, n_craft)
         o += n_craft
-        id_keys = [self.n_honest + i for i, k in enumerate(self.crafted) if k[0].startswith("identity")]
-        val[o:o + n_nc] = rng.choice(id_keys, n_nc)
+        val[o:o + n_nc] = rng.choice([self.n_honest + vi for vi in sorted(self.nc_neg_t)], n_nc)
         o += n_nc
         val[o:] = -1                     # unknown / empty / nil: no validator
         kind = np.zeros(n_prim, np.int8)  # 0 base 1 crafted 2 noncanon-R 3 unknown 4 empty 5 nil
@@ -229,6 +273,9 @@ class C4Stream:
         f["addr_len"][:n_prim][kind == 4] = 0
         f["is_nil"][:n_prim][kind == 5] = 1
         f["txoff"][:n_prim] = (f["tx"][:n_prim] * 64).astype(np.uint32)
+        # non-canonical-R primaries now: they may redraw their tx, which their conflicts copy below
+        for i in np.nonzero(kind == 2)[0]:
+            self._small_order_vote(f, int(i), primary=True)
 
         # conflicts: same validator + tx as the source, new timestamp, fresh valid signature
         def src_field(key, from_prev, j):
@@ -266,14 +313,12 @@ class C4Stream:
         if n_fresh:
             self.ctx.keygen(self.seeds)           # keygen also sets the signer keys: the honest ones back
         fresh_r = [_expand(sd) for sd in seeds]
-        nc_form = rng.integers(0, 3, len(ci))
         q_f = 0
-        for q, i in enumerate(ci):
+        for i in ci:
             vi = int(f["val"][i]) - self.n_honest
             if f["kind"][i] == 2:
-                # identity key, r = 0: R = identity (canonical / x=0 with sign bit / y+p), s = 0
-                R = (E.encode((0, 1)), E.encode_raw(1, 1), E.encode_raw(1 + E.P, 0))[nc_form[q]]
-                f["sig"][i] = np.frombuffer(R + bytes(32), np.uint8)
+                if i >= n_prim:      # a conflict copy (the primaries are signed above)
+                    self._small_order_vote(f, int(i), primary=False)
                 continue
             msg = T.sign_bytes(int(f["height"][i]), self.hashes[f["tx"][i]].tobytes(), 1_700_000_000,
                                int(f["ts_nanos"][i]), CHAIN)

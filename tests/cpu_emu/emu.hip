@@ -71,12 +71,30 @@ int emu_fe(const uint32_t* a, const uint32_t* b, uint32_t* out, int op) {
     case 4: r = fe_canon(x); break;
     case 5: r = fe_invert(x); break;
     case 7: r = fe_invert_var(x); break;
-    default: {
+    case 8:
+    case 9:
+    case 10: {   // as txv_k_fe_selftest: fe10_mul / fe10_mul2 at their operand bounds (host fallback columns)
+      const fe10 x1 = fe10_strict(fe10_from_fe(x)), y1 = fe10_strict(fe10_from_fe(y));
+      const fe10 x2 = fe10_add(x1, x1), x3 = fe10_add(x2, x1), x4 = fe10_add(x2, x2);
+      const fe10 y3 = fe10_add(fe10_add(y1, y1), y1);
+      fe10 h1, h2;
+      if (op == 8) {
+        h1 = fe10_mul(x4, y3);
+        h2 = h1;
+      } else {
+        fe10_mul2(x4, y3, y3, x3, h1, h2);
+      }
+      r = fe_from_fe10(op == 10 ? h2 : h1);
+      break;
+    }
+    case 6: {
       uint32_t t[16];
       for (int j = 0; j < 8; ++j) { t[j] = x.v[j]; t[8 + j] = y.v[j]; }
       sc s = sc_reduce512(t);
       for (int j = 0; j < 8; ++j) r.v[j] = s.v[j];
+      break;
     }
+    default: return -1;
   }
   for (int j = 0; j < 8; ++j) out[j] = r.v[j];
   return 0;

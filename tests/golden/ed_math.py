@@ -66,6 +66,45 @@ def order(p):
     return None
 
 
+def neg(p):
+    return ((P - p[0]) % P, p[1])
+
+
+def torsion_encodings():
+    """The 14 byte strings x/crypto's point decoding maps to a point of E[8]:
+    [(tag, bytes, point, canonical)].  8 canonical ones, and the 6 non-canonical ones there are:
+    the identity as (y = 1, sign 1), (y = p + 1, sign 0 / 1); (0, -1) with the sign bit; and
+    y = p (= 0) with either sign, the two order-4 points.  (Every other torsion y is >= 19, so
+    y + p does not fit 255 bits.)"""
+    out = [("canon_ord%d" % order(t), encode(t), t, True) for t in torsion_points()]
+    out += [("noncanon_ident_negzero", encode_raw(1, 1), (0, 1), False),
+            ("noncanon_ident_yp", encode_raw(1 + P, 0), (0, 1), False),
+            ("noncanon_ident_yp_negzero", encode_raw(1 + P, 1), (0, 1), False),
+            ("noncanon_ord2_negzero", encode_raw(P - 1, 1), (0, P - 1), False),
+            ("noncanon_ord4_yp_s0", encode_raw(P, 0), (recover_x(0, 0), 0), False),
+            ("noncanon_ord4_yp_s1", encode_raw(P, 1), (recover_x(0, 1), 0), False)]
+    return out
+
+
+def neg_multiples(t):
+    """[-[j]T for j in 0..7] of a torsion point T"""
+    return [mul(j, neg(t)) for j in range(8)]
+
+
+def rprime_sig(pub, a, neg_t, rb, q, msg):
+    """(rb || s) under the key A = [a]B + T (pub its encoding, neg_t = neg_multiples(T)) whose
+    R' = [s]B - [k]A is EXACTLY the torsion point q that rb names, after a walk with generic
+    digits: k = SHA-512(rb || A || msg) mod L, and s = k a gives [s]B - [k]A = -[k mod 8]T.
+    None when this message's k does not land on q (the caller draws another message).
+    A verifier that encodes R' canonically and compares bytes accepts exactly the canonical rb;
+    one that compares points accepts every rb."""
+    import hashlib
+    k = int.from_bytes(hashlib.sha512(rb + pub + msg).digest(), "little") % L
+    if neg_t[k % 8] != q:
+        return None
+    return rb + (k * a % L).to_bytes(32, "little")
+
+
 def torsion_points():
     """all 8 points of E[8]"""
     pts = set()

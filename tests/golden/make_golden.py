@@ -8,7 +8,10 @@ Provenance of each expected value:
   verify_vectors.json   adversarial (pub, msg, sig) with the x/crypto@c2843e01d9a2 verdict as
                         restated by the oracle; the OpenSSL verdict is
                         recorded beside it.  Cases where the two differ are decided by Appendix A
-                        and are "parity unpinned" beyond that restatement.
+                        and are "parity unpinned" beyond that restatement.  The edge kinds
+                        (edge_vectors below: small-order R', edge scalars, cancellation) are
+                        appended last from an RNG of their own, and their verdicts are also
+                        checked against the Python model of the rule (verify_model.py).
   signbytes.json        amino SignBytes / Size cases; two are pinned by the reference's own tests
                         (types/vote_test.go:62 zero-time bytes, txvotepool/txvotepool_test.go:102
                         Size()==114); the rest come from the oracle's restatement (Appendix B).
@@ -42,6 +45,143 @@ def forge(a_pub: bytes, msg: bytes, rnd, secret=None):
     k = sc(R + a_pub + msg)
     s = (r + k * (secret or 0)) % E.L
     return R + s.to_bytes(32, "little")
+
+
+# s values of the s_edge vectors: the ends of [0, L), the values around 2^252 where the long top
+# digit of the radix-2^21 tables (Tab<21>, unsigned, up to 2^21 + 1) is at or near its maximum, and
+# the all-half-digit patterns of tests/test_cpu_emu.py::test_table_digits_cover_every_scalar_below_L
+S_EDGE = [0, 1, 2, E.L - 1, E.L - 2, 2 ** 252, 2 ** 252 - 1, 2 ** 252 + 2 ** 124, 2 ** 252 - 2 ** 231,
+          2 ** 252 - 2 ** 230, (2 ** 231 - 1) * (2 ** 21 + 1) % E.L, sum(1 << (21 * i + 20) for i in range(12)) % E.L,
+          sum(1 << (21 * i + 20) for i in range(11)), sum(1 << (21 * i + 19) for i in range(12)) % E.L]
+S_EDGE_ORD8 = [0, 1, E.L - 1, 2 ** 252 - 2 ** 231, 2 ** 252 + 2 ** 124, sum(1 << (21 * i + 20) for i in range(11))]
+K_TOP, K_LOW = 2 ** 252 - 2 ** 231, 2 ** 231
+GRIND_CAP = 1 << 25
+
+
+def edge_vectors(add, vec, base, mixed_keys, tors):
+    """Vectors at the edges of the verify path, appended after everything above and drawn from an
+    RNG of their own (so every earlier entry of every fixture stays byte-identical):
+
+      smallorder_rprime_*   R' = [s]B - [k]A lands EXACTLY on a point of E[8] after a full walk with
+                            generic digits (ed_math.rprime_sig over the mixed-order keys above, and
+                            over pure torsion keys with s = 0); R is one of the 14 encodings of
+                            that point.  x/crypto accepts the 8 canonical ones only.
+      s_edge*               s at the ends of its range and at the table digits' extremes, under the
+                            identity key (R = [s]B) and an order-8 key (R = [s]B - [j]T, k = j mod 8)
+      cancel_*              key B or -B: the B walk and the A walk cancel to the identity
+      k_top / k_low         an honest key, the message ground until k >= 2^252 - 2^231 / k < 2^231
+
+    Each verdict is the oracle's (add) and must equal the Python model's (verify_model.verify);
+    every *_noncanon_* vector must be accepted by the point-comparing variant, i.e. it separates
+    a right implementation from a wrong one."""
+    import verify_model as V
+    rnd = random.Random(20261020)
+    n0 = len(vec)
+
+    def rmsg():
+        return bytes(rnd.getrandbits(8) for _ in range(rnd.randrange(1, 160)))
+
+    def le(x):
+        return x.to_bytes(32, "little")
+
+    # ---- small-order R'
+    encs = E.torsion_encodings()
+    mixed = [(pub, a, E.neg_multiples(T)) for pub, a, T in mixed_keys]
+    pure = [(E.encode(T), 0, E.neg_multiples(T)) for T in tors if E.order(T) == 8]
+    for ei, (tag, rb, q, canon) in enumerate(encs):
+        elig = [k for k in mixed if q in k[2]]
+        assert len(elig) >= 2
+        # two different mixed-order keys (rotating through the eligible ones) and one pure torsion key
+        for pub, a, neg_t in [elig[ei % len(elig)], elig[(ei + 1) % len(elig)], pure[ei % len(pure)]]:
+            for _ in range(4096):
+                m = rmsg()
+                sig = E.rprime_sig(pub, a, neg_t, rb, q, m)
+                if sig is not None:
+                    break
+            else:
+                raise AssertionError("no message found for " + tag)
+            add("smallorder_rprime_" + tag, pub, m, sig)
+            assert vec[-1]["expect"] == canon, tag
+
+    # ---- s at its edges
+    ident = E.encode((0, 1))
+    for s in S_EDGE:
+        assert 0 <= s < E.L
+        add("s_edge", ident, rmsg(), E.encode(E.mul(s, E.B)) + le(s))
+        assert vec[-1]["expect"]
+    for s in (E.L - 1, 2 ** 252 - 1):                       # R taken from s + 1
+        add("s_edge_twin", ident, rmsg(), E.encode(E.mul(s + 1, E.B)) + le(s))
+        assert not vec[-1]["expect"]
+    t8 = next(T for T in tors if E.order(T) == 8)
+    pub8, neg8 = E.encode(t8), E.neg_multiples(t8)
+
+    def ord8_sig(s_point, s):
+        """R = [s_point]B - [j]T for the j that this message's k turns out to be (mod 8)"""
+        sb = E.mul(s_point, E.B)
+        cand = [E.encode(E.add(sb, neg8[j])) for j in range(8)]
+        while True:
+            m = rmsg()
+            for j, rb in enumerate(cand):
+                if sc(rb + pub8 + m) % 8 == j:
+                    return m, rb + le(s)
+
+    for s in S_EDGE_ORD8:
+        add("s_edge_ord8", pub8, *ord8_sig(s, s))
+        assert vec[-1]["expect"]
+    add("s_edge_ord8_twin", pub8, *ord8_sig(2 ** 252 - 2 ** 231 + 1, 2 ** 252 - 2 ** 231))
+    assert not vec[-1]["expect"]
+
+    # ---- B and A cancel
+    pub_b, pub_nb = E.encode(E.B), E.encode(E.neg(E.B))
+    for _ in range(2):
+        m = rmsg()
+        for tag, rb, q, canon in encs:
+            if q == (0, 1):      # s = k: [k]B - [k]B = identity, named canonically or not
+                add("cancel_ident_canon" if canon else "cancel_" + tag, pub_b, m, rb + le(sc(rb + pub_b + m)))
+                assert vec[-1]["expect"] == canon
+        add("cancel_R_eq_B", pub_b, m, pub_b + le((sc(pub_b + pub_b + m) + 1) % E.L))
+        assert vec[-1]["expect"]
+        add("cancel_negB", pub_nb, m, ident + le((E.L - sc(ident + pub_nb + m)) % E.L))
+        assert vec[-1]["expect"]
+
+    # ---- k at the top / bottom of its range, an honest key
+    seed, pub = bytes.fromhex(base[0]["seed"]), bytes.fromhex(base[0]["pub"])
+    h = hashlib.sha512(seed).digest()
+    a = (int.from_bytes(h[:32], "little") & ((1 << 254) - 8)) | (1 << 254)
+    assert E.encode(E.mul(a, E.B)) == pub
+
+    def grind(kind, n, pred):
+        for i in range(n):
+            r = rnd.randrange(1, E.L)
+            rb = E.encode(E.mul(r, E.B))
+            prefix = b"%s/%d/" % (kind.encode(), i)
+            h0 = hashlib.sha512(rb + pub + prefix)
+            for ctr in range(GRIND_CAP):
+                hh = h0.copy()
+                hh.update(ctr.to_bytes(8, "little"))
+                k = int.from_bytes(hh.digest(), "little") % E.L
+                if pred(k):
+                    break
+            else:
+                raise AssertionError("grind cap reached for " + kind)
+            sig = rb + le((r + k * a) % E.L)
+            m = prefix + ctr.to_bytes(8, "little")
+            add(kind, pub, m, sig)
+            assert vec[-1]["expect"]
+            s = bytearray(sig)
+            s[32 + rnd.randrange(31)] ^= 1 << rnd.randrange(8)
+            add(kind + "_s_bitflip", pub, m, bytes(s))
+            assert not vec[-1]["expect"]
+
+    grind("k_top", 3, lambda k: k >= K_TOP)
+    grind("k_low", 2, lambda k: k < K_LOW)
+
+    # ---- the second implementation: the Python model on every new vector
+    for v in vec[n0:]:
+        p, m, s = bytes.fromhex(v["pub"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
+        assert V.verify(p, m, s) == v["expect"], v["kind"]
+        if "_noncanon_" in v["kind"]:
+            assert not v["expect"] and V.verify_point_compare(p, m, s), v["kind"]
 
 
 def main():
@@ -109,11 +249,13 @@ def main():
         add("ident_R_noncanon_y", ident, m, E.encode_raw(1 + E.P, 0) + (0).to_bytes(32, "little"))
         add("ident_R_negzero", ident, m, E.encode_raw(1, 1) + (0).to_bytes(32, "little"))
     # mixed-order keys: A' = [a]B + T (cofactorless check: valid iff [k]T = 0)
+    mixed_keys = []    # (pub, a, T): kept for the small-order R' vectors below
     for i, T in enumerate(tors):
         if T == (0, 1):
             continue
         a = rnd.randrange(1, E.L)
         Ap = E.encode(E.add(E.mul(a, E.B), T))
+        mixed_keys.append((Ap, a, T))
         for m in msgs:
             add("mixed_order_ord%d" % E.order(T), Ap, m, forge(Ap, m, rnd, secret=a))
     # undecodable public keys
@@ -129,6 +271,7 @@ def main():
     for c in base[:4]:
         pub = bytearray(bytes.fromhex(c["pub"])); pub[31] ^= 0x80
         add("pub_signflip", bytes(pub), bytes.fromhex(c["msg"]), bytes.fromhex(c["sig"]))
+    edge_vectors(add, vec, base, mixed_keys, tors)
     out["verify_vectors"] = vec
 
     # ---------------------------------------------------------------- SignBytes / Size

@@ -82,6 +82,65 @@ def test_c4_stream_covers_every_outcome(oracle_lib):
         assert must in names
 
 
+def _checktx(oracle_lib, b, f):
+    """the batch's gossiped votes through the oracle's CheckTx: (indices into f, pool statuses)"""
+    import txflow_amd as T
+    gossip = np.nonzero(f["is_nil"] == 0)[0]
+    m = len(gossip)
+    sub = T.VoteBatch(m, height=f["height"][gossip], txhash_arena=b.txhash_arena, txhash_off=f["txoff"][gossip],
+                      txhash_len=np.full(m, 64, np.uint32), ts_sec=np.full(m, 1_700_000_000, np.int64),
+                      ts_nanos=f["ts_nanos"][gossip], addr=f["addr"][gossip], addr_len=f["addr_len"][gossip],
+                      sig=f["sig"][gossip], sig_len=f["sig_len"][gossip])
+    long_sigs = {int(q): sub.sig[64 * q:64 * q + 64].tobytes() + bytes(int(sub.sig_len[q]) - 64)
+                 for q in np.nonzero(sub.sig_len > 64)[0]}
+    pool = oracle_lib.Pool(size=(1 << 31) - 1, cache_size=1 << 16, max_txs_bytes=1 << 40)
+    return gossip, pool.check_batch(sub, long_sigs)
+
+
+def test_c4_noncanonical_r_class_survives_checktx_and_separates(oracle_lib):
+    """The non-canonical-R class (adversarial.C4Stream._small_order_vote): every vote has signature
+    bytes of its own, so CheckTx admits at least 0.8 of the class's share (it kept 78 of 529,442
+    when the class was three fixed signatures).  Both verdicts occur; every vote whose R is a
+    non-canonical encoding is rejected by the oracle and by the Python model of the rule, yet
+    accepted by the model's point-comparing variant, with R' the small-order point R names and
+    s != 0 (generic digits): the class tells a verifier that canonicalises R' from one that
+    does not.  Checked on the primaries, their conflict copies and their replays."""
+    import adversarial as A
+    import ed_math as E
+    import txflow_amd as T
+    import verify_model as V
+    n, share = 16000, 0.005
+    s = A.C4Stream(OracleCtx(), batch=n, batches_per_epoch=2, oracle_threads=4, verify_slice=0)
+    canon = {e[1] for e in E.torsion_encodings() if e[3]}
+    noncanon = {e[1] for e in E.torsion_encodings() if not e[3]}
+    seen_enc, verdicts = set(), {True: 0, False: 0}
+    for _ in range(2):                         # the second batch has conflicts sourced from the first
+        b, f = s.next_batch()
+        gossip, ops = _checktx(oracle_lib, b, f)
+        cls = f["cls"][gossip]
+        prim = cls == A.CLS["noncanonical_r"]
+        assert int(prim.sum()) >= 0.95 * share * n
+        assert int(np.count_nonzero(prim & (ops == T.POOL_OK))) >= 0.8 * share * n
+        idx = np.nonzero(f["kind"] == 2)[0]    # primaries, their conflicts and replays
+        assert len(idx) > int(prim.sum())
+        sigs = {f["sig"][i].tobytes() for i in np.nonzero((f["kind"] == 2) & (f["cls"] != A.CLS["exact_replay"]))[0]}
+        assert len(sigs) == int(np.count_nonzero((f["kind"] == 2) & (f["cls"] != A.CLS["exact_replay"])))
+        for i in idx:
+            name, pub, _ = s.crafted[int(f["val"][i]) - s.n_honest]
+            assert name in ("mixed4", "mixed8")
+            sig = f["sig"][i].tobytes()
+            msg = T.sign_bytes(int(f["height"][i]), s.hashes[f["tx"][i]].tobytes(), 1_700_000_000,
+                               int(f["ts_nanos"][i]), A.CHAIN)
+            exp = sig[:32] in canon
+            assert exp or sig[:32] in noncanon
+            assert oracle_lib.verify(pub, msg, sig) == exp == V.verify(pub, msg, sig)
+            assert V.verify_point_compare(pub, msg, sig) and int.from_bytes(sig[32:], "little") != 0
+            seen_enc.add(sig[:32])
+            verdicts[exp] += 1
+    assert verdicts[True] > 0 and verdicts[False] > verdicts[True]
+    assert noncanon <= seen_enc and len(seen_enc & canon) >= 4
+
+
 def test_c4_keyless_classes_survive_checktx(oracle_lib):
     """Unknown-validator, empty-address and nil votes carry distinct signatures, so CheckTx's LRU
     (keyed by SHA-256(Signature), txvotepool.go:467-469) admits them and Appendix C's shares of

@@ -66,6 +66,19 @@ def test_field_and_scalar_ops(emu):
                 assert v == exp
 
 
+def inverse_candidates():
+    """structured inputs that need many divsteps (also the device's, tests/test_gpu_parity.py):
+    powers of two, p - 2^k, bit patterns, Fibonacci numbers and ratios"""
+    fib = [0, 1]
+    while len(fib) < 400:
+        fib.append(fib[-1] + fib[-2])
+    cands = [1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2 ** 254, 2 ** 255 - 20]
+    cands += [2 ** k % P for k in range(0, 255, 7)] + [(P - 2 ** k) % P for k in range(1, 255, 11)]
+    cands += [int("10" * 127, 2), int("110" * 84, 2) % P, int("1" * 254, 2)]
+    cands += [fib[k] % P for k in range(300, 400, 5)] + [fib[k] * pow(fib[k + 1], P - 2, P) % P for k in range(50, 380, 30)]
+    return cands
+
+
 def test_divstep_inverse_near_its_bound(emu):
     """fe_invert_var (K1b's shared inversion) on inputs chosen to need many divsteps: structured
     ones (powers of two, p - 2^k, all-ones patterns, Fibonacci-ratio values) and the worst of a
@@ -74,13 +87,7 @@ def test_divstep_inverse_near_its_bound(emu):
     import numpy as np
     rnd = random.Random(17)
     out = (ctypes.c_uint32 * 8)()
-    fib = [0, 1]
-    while len(fib) < 400:
-        fib.append(fib[-1] + fib[-2])
-    cands = [1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2 ** 254, 2 ** 255 - 20]
-    cands += [2 ** k % P for k in range(0, 255, 7)] + [(P - 2 ** k) % P for k in range(1, 255, 11)]
-    cands += [int("10" * 127, 2), int("110" * 84, 2) % P, int("1" * 254, 2)]
-    cands += [fib[k] % P for k in range(300, 400, 5)] + [fib[k] * pow(fib[k + 1], P - 2, P) % P for k in range(50, 380, 30)]
+    cands = inverse_candidates()
 
     def counts(xs):
         arr = np.array([[(x >> (32 * i)) & 0xFFFFFFFF for i in range(8)] for x in xs], np.uint32)
@@ -165,6 +172,48 @@ def test_fe10_limb_arithmetic_at_its_bounds(emu):
         assert f(o8) % P == x % P and f(o8) < 2 ** 255 + 19
 
 
+def fe10_bound_operands(rnd, n):
+    """(x, y) pairs below 2^255 for the self-test ops 8..10 (4 x10 * 3 y10): 2^255 - 1 (every limb
+    of both operands at its documented maximum), all-zero against it, and values whose ten limbs
+    are each 0, 2^w - 1 or random"""
+    top = 2 ** 255 - 1
+
+    def pick():
+        return v10([rnd.choice([0, (1 << w) - 1, rnd.randrange(1 << w)]) for w in W10])
+
+    return [(top, top), (0, top), (top, 0), (0, 0), (1, top)] + [(pick(), pick()) for _ in range(n)]
+
+
+def fe10_bound_expected(x, y, op):
+    return {8: 12, 9: 12, 10: 9}[op] * x * y % P
+
+
+def emu_fe_words(emu, pairs, op):
+    """emu_fe (the host build of the kernel source: fe10_col / fe10_col2 take their plain-C
+    fallback) on each pair: [n][8] words"""
+    out = (ctypes.c_uint32 * 8)()
+    rows = []
+    for x, y in pairs:
+        assert emu.emu_fe(w(x), w(y), out, op) == 0
+        rows.append(list(out))
+    return rows
+
+
+def test_selftest_fe10_ops_host_fallback(emu):
+    """ops 8..10 of the field self-test as the host compiles them: 12 x y, 12 x y and 9 x y mod p
+    from Python integers, weakly reduced (< 2^255 + 19); an op outside 0..10 is refused.  The
+    device runs the same ops through its v_mad_u64_u32 chains and must give the same words
+    (tests/test_gpu_parity.py::test_fe10_ops_at_operand_bounds)."""
+    rnd = random.Random(8)
+    pairs = fe10_bound_operands(rnd, 600) + [(rnd.getrandbits(256), rnd.getrandbits(256)) for _ in range(200)]
+    for op in (8, 9, 10):
+        for (x, y), row in zip(pairs, emu_fe_words(emu, pairs, op)):
+            assert f(row) < 2 ** 255 + 19 and f(row) % P == fe10_bound_expected(x, y, op), (op, hex(x), hex(y))
+    out = (ctypes.c_uint32 * 8)()
+    for op in (-1, 11, 99):
+        assert emu.emu_fe(w(1), w(1), out, op) == -1
+
+
 def _ed_add(p1, p2):
     d = -121665 * pow(121666, P - 2, P) % P
     (x1, y1), (x2, y2) = p1, p2
@@ -214,11 +263,19 @@ def test_ge10_madd_half_niels(emu):
             assert list(out_rd[:30]) == list(out[:30])
 
 
+EDGE_KINDS = ("smallorder_rprime_", "s_edge", "cancel_", "k_top", "k_low")
+
+
 def test_verify_vectors_through_kernel_source(emu):
+    """A sample of the older golden vectors and EVERY vector of the edge kinds (R' landing on a
+    small-order point after a generic walk, s and k at the ends of their range, B and A
+    cancelling) through the kernel source's decode / walk / encode on the host."""
     vec = json.load(open(os.path.join(HERE, "golden", "verify_vectors.json")))
     rnd = random.Random(3)
-    sample = [v for v in vec if v["kind"] != "valid"]
-    sample = rnd.sample(sample, 60) + [v for v in vec if v["kind"] == "valid"][:6]
+    edge = [v for v in vec if v["kind"].startswith(EDGE_KINDS)]
+    assert len(edge) == 87 and sum("_noncanon_" in v["kind"] for v in edge) == 24
+    sample = [v for v in vec if v["kind"] != "valid" and not v["kind"].startswith(EDGE_KINDS)]
+    sample = rnd.sample(sample, 60) + [v for v in vec if v["kind"] == "valid"][:6] + edge
     for v in sample:
         pub, msg, sig = bytes.fromhex(v["pub"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
         got = bool(emu.emu_verify(pub, msg, len(msg), sig, len(sig)))

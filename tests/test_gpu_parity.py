@@ -8,6 +8,8 @@ import random
 import numpy as np
 import pytest
 
+from test_cpu_emu import emu  # noqa: F401  (fixture: the host build of the kernel source, tests/cpu_emu)
+
 pytestmark = pytest.mark.gpu
 
 P = 2 ** 255 - 19
@@ -53,6 +55,57 @@ def test_field_ops_bit_exact(gpu_ctx, op):
         else:
             exp = pow(x, P - 2, P)
         assert r % P == exp, (op, hex(x), hex(y), hex(r))
+
+
+def _selftest_inputs(seed):
+    """the edge list, the structured divstep-heavy values of the CPU inverse test and 2000 random
+    256-bit values (so the lanes of one wave run different divstep counts): (A, B)"""
+    from test_cpu_emu import inverse_candidates
+    rnd = random.Random(seed)
+    cands = inverse_candidates()
+    A = _edge_values() + cands + [rnd.getrandbits(256) for _ in range(2000)]
+    B = list(reversed(_edge_values())) + list(reversed(cands)) + [rnd.getrandbits(256) for _ in range(2000)]
+    return A, B
+
+
+def test_divstep_inverse_bit_exact(gpu_ctx):
+    """op 7: fe_invert_var (K1c runs it once per verified vote) on the device equals
+    pow(x, p - 2, p) exactly -- the result is canonical -- with 0 and p mapping to 0."""
+    A, B = _selftest_inputs(7)
+    a = np.array([to_words(x) for x in A], np.uint32)
+    out = gpu_ctx.fe_selftest(a, np.zeros_like(a), 7)
+    for x, w in zip(A, out):
+        assert from_words(w) == pow(x, P - 2, P), hex(x)
+
+
+@pytest.mark.parametrize("op", [8, 9, 10])
+def test_fe10_ops_at_operand_bounds(gpu_ctx, emu, op):
+    """ops 8..10: the walk's radix-2^25.5 multiplies as the device compiles them (fe10_col /
+    fe10_col2 are inline-asm chains of v_mad_u64_u32 there, plain C on the host) at the documented
+    operand bounds, f = 4 x10 < 4 2^w and g = 3 y10 < 3 2^w: x = y = 2^255 - 1 has every limb of
+    both operands at its maximum, further operands have each limb 0, maximal or random.  Expected
+    from Python integers: 12 x y (fe10_mul and the first product of fe10_mul2) and 9 x y (the
+    second) mod p, weakly reduced; and the same 8 words as the host fallback."""
+    from test_cpu_emu import emu_fe_words, fe10_bound_expected, fe10_bound_operands
+    A, B = _selftest_inputs(op)
+    pairs = fe10_bound_operands(random.Random(100 + op), 1500) + list(zip(A, B))
+    a = np.array([to_words(x) for x, _ in pairs], np.uint32)
+    b = np.array([to_words(y) for _, y in pairs], np.uint32)
+    out = gpu_ctx.fe_selftest(a, b, op)
+    host = emu_fe_words(emu, pairs, op)
+    for (x, y), w, hw in zip(pairs, out, host):
+        r = from_words(w)
+        assert r < 2 ** 255 + 19 and r % P == fe10_bound_expected(x, y, op), (op, hex(x), hex(y), hex(r))
+        assert [int(v) for v in w] == hw, (op, hex(x), hex(y))
+
+
+def test_selftest_refuses_unknown_ops(gpu_ctx):
+    """an op outside 0..10 is TXV_EINVAL (it used to fall into sc_reduce512)"""
+    import txflow_amd as T
+    a = np.array([to_words(1)], np.uint32)
+    for op in (-1, 11, 12, 255):
+        with pytest.raises(T.TxvInfraError):
+            gpu_ctx.fe_selftest(a, a, op)
 
 
 def test_scalar_reduce_bit_exact(gpu_ctx):
@@ -298,7 +351,13 @@ def test_golden_vectors_verify_bytes(gpu_ctx):
     """Every committed ed25519 fixture through PubKeyEd25519.VerifyBytes on the GPU
     (txv_verify_bytes): the OpenSSL RFC 8032 vectors must verify, and each adversarial vector
     (torsion / small-order / mixed-order / y >= p / "-0" / undecodable keys, non-canonical R,
-    s + L, top bits, bit flips, lengths 0/63/65) must get its recorded x/crypto-rule verdict."""
+    s + L, top bits, bit flips, lengths 0/63/65; R' landing on a small-order point after a generic
+    walk under each of its 14 encodings, s and k at the ends of their range and at the table
+    digits' extremes, B's and A's walks cancelling) must get its recorded x/crypto-rule verdict:
+    378 adversarial + 48 OpenSSL vectors.  Then the same set tiled and shuffled to 66,000 items
+    (below the 768K threshold: the split kernel, K1c inverting four Z per lane in one chain), so
+    that each lane's chain mixes skipped items, ordinary Z values and the Z values of small-order
+    results; every item against its recorded verdict."""
     import json
     here = os.path.dirname(os.path.abspath(__file__))
     with open(os.path.join(here, "golden", "verify_vectors.json")) as f:
@@ -314,6 +373,13 @@ def test_golden_vectors_verify_bytes(gpu_ctx):
     bad = [(c[4], bool(g)) for c, g in zip(cases, got) if bool(g) != c[3]]
     assert not bad, bad[:10]
     assert sum(c[3] for c in cases) > 60 and sum(not c[3] for c in cases) > 100
+    assert len(vec) == 378 and sum("_noncanon_" in c[4] and c[4].startswith(("smallorder_", "cancel_")) for c in cases) == 24
+    n = 66_000
+    perm = np.random.default_rng(66).integers(0, len(cases), n)
+    exp = np.array([c[3] for c in cases])
+    got_t = gpu_ctx.verify_bytes([pubs[i] for i in perm], [msgs[i] for i in perm], [sigs[i] for i in perm])
+    bad_t = np.nonzero(got_t != exp[perm])[0]
+    assert len(bad_t) == 0, (len(bad_t), [(int(i), cases[int(perm[i])][4], bool(got_t[i])) for i in bad_t[:10]])
 
 
 def test_c4_adversarial_stream_gate(oracle_lib):

@@ -44,8 +44,67 @@ def test_adversarial_verify_vectors(oracle_lib):
     # the fixture covers the Appendix C classes
     for k in ("valid", "r_bitflip", "s_bitflip", "s_plus_L", "s_top_bit", "len63", "msg_changed",
               "torsion_canon_ord8", "torsion_noncanon_y_ord1", "torsion_negzero_ord2", "mixed_order_ord8",
-              "ident_R_noncanon_y", "ident_R_negzero", "undecodable_pub"):
+              "ident_R_noncanon_y", "ident_R_negzero", "undecodable_pub",
+              "smallorder_rprime_canon_ord1", "smallorder_rprime_canon_ord2", "smallorder_rprime_canon_ord4",
+              "smallorder_rprime_canon_ord8", "smallorder_rprime_noncanon_ident_negzero",
+              "smallorder_rprime_noncanon_ident_yp", "smallorder_rprime_noncanon_ident_yp_negzero",
+              "smallorder_rprime_noncanon_ord2_negzero", "smallorder_rprime_noncanon_ord4_yp_s0",
+              "smallorder_rprime_noncanon_ord4_yp_s1", "s_edge", "s_edge_twin", "s_edge_ord8", "s_edge_ord8_twin",
+              "cancel_ident_canon", "cancel_noncanon_ident_negzero", "cancel_noncanon_ident_yp",
+              "cancel_noncanon_ident_yp_negzero", "cancel_R_eq_B", "cancel_negB", "k_top", "k_top_s_bitflip",
+              "k_low", "k_low_s_bitflip"):
         assert k in kinds
+
+
+EDGE_KINDS = ("smallorder_rprime_", "s_edge", "cancel_", "k_top", "k_low")
+
+
+def test_edge_vectors_rest_on_two_implementations():
+    """The edge kinds (tests/golden/make_golden.py edge_vectors) against the Python model of the
+    acceptance rule (tests/golden/verify_model.py): its verdict equals the recorded (oracle) one
+    for every such vector, so the expected values rest on two implementations, neither of them
+    under test.  The point-comparing variant of the model accepts every *_noncanon_* vector, all
+    of which the rule rejects: the vectors separate a right verifier from a wrong one.  And each
+    is what it claims to be: R' is the small-order point R names, s / k sit at their edges."""
+    import ed_math as E
+    import verify_model as V
+    vec = [v for v in load("verify_vectors.json") if v["kind"].startswith(EDGE_KINDS)]
+    assert len(vec) == 87
+    tors = {V.encode(V.from_affine(t)) for t in E.torsion_points()}
+    named = {}
+    n_noncanon = 0
+    for v in vec:
+        pub, msg, sig = bytes.fromhex(v["pub"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
+        kind = v["kind"]
+        assert V.verify(pub, msg, sig) == v["expect"] == v["openssl"], kind
+        rp = V.r_prime(pub, msg, sig)
+        s = int.from_bytes(sig[32:], "little")
+        k = V.challenge(sig[:32], pub, msg)
+        if "_noncanon_" in kind:
+            n_noncanon += 1
+            assert not v["expect"] and V.verify_point_compare(pub, msg, sig), kind
+            assert V.encode(rp) in tors and V.encode(rp) != sig[:32]
+        if kind.startswith("smallorder_rprime_"):
+            assert V.encode(rp) in tors and V.affine(V.decode(sig[:32])) == V.affine(rp), kind
+            assert (s == 0) == (V.encode(V.decode(pub)) in tors)        # generic digits unless a pure torsion key
+            named.setdefault(sig[:32], set()).add(pub)
+        elif kind in ("k_top", "k_top_s_bitflip"):
+            assert k >= 2 ** 252 - 2 ** 231
+        elif kind in ("k_low", "k_low_s_bitflip"):
+            assert k < 2 ** 231
+        elif kind.startswith("cancel_ident") or kind.startswith("cancel_noncanon") or kind == "cancel_negB":
+            assert V.affine(rp) == (0, 1) and s != 0
+    assert n_noncanon == 24
+    # all 14 encodings of the points of E[8], each under two mixed-order keys and a pure torsion key
+    assert set(named) == {e[1] for e in E.torsion_encodings()} and len(named) == 14
+    assert all(len(pubs) == 3 for pubs in named.values())
+    s_seen = {int.from_bytes(bytes.fromhex(v["sig"])[32:], "little") for v in vec if v["kind"] == "s_edge"}
+    assert {0, 1, 2, L - 1, L - 2, 2 ** 252, 2 ** 252 - 1, 2 ** 252 + 2 ** 124, 2 ** 252 - 2 ** 231,
+            2 ** 252 - 2 ** 230} <= s_seen and len(s_seen) == 14
+    # the table-memory budget of test_shipped_windows_golden_vectors: the edge kinds add 2 keys (B, -B)
+    older = {v["pub"] for v in load("verify_vectors.json") if not v["kind"].startswith(EDGE_KINDS)}
+    older |= {c["pub"] for c in load("ed25519_openssl.json")}
+    assert len({v["pub"] for v in vec} - older) <= 4
 
 
 def test_decode_rules(oracle_lib):

@@ -9,10 +9,13 @@ tests pin exactly that instantiation against the oracle (x/crypto ``ed25519.Veri
 SURVEY.md Appendix A; reference call sites ``types/tx_vote.go:110-119`` and
 ``types/vote_set.go:92-166``):
 
-* every committed ed25519 vector -- 48 OpenSSL RFC 8032 signatures and 291 adversarial ones
+* every committed ed25519 vector -- 48 OpenSSL RFC 8032 signatures and 378 adversarial ones
   (all 8 torsion points with canonical / y >= p / "-0" encodings, mixed-order keys, undecodable
-  keys, non-canonical R, s + L, top bits, bit flips, lengths 0 / 63 / 65) -- through
-  ``txv_verify_bytes`` with its 81 distinct keys built into radix-2^21 tables, once at its own
+  keys, non-canonical R, s + L, top bits, bit flips, lengths 0 / 63 / 65; R' landing on a
+  small-order point after a generic walk under each of its 14 encodings, s and k at the ends of
+  their range -- the long top digit of ``Tab<21>`` at and near its maximum --, B's and A's walks
+  cancelling) -- through
+  ``txv_verify_bytes`` with its 83 distinct keys built into radix-2^21 tables, once at its own
   size (split kernel) and once tiled past 768K items (the V = 8 work-stealing kernel);
 * the C4 adversarial stream (identity / order-2/4/8 / mixed-order / y >= p /
   "-0" / undecodable validator keys with forged signatures, bad signatures of every class,
@@ -20,7 +23,7 @@ SURVEY.md Appendix A; reference call sites ``types/tx_vote.go:110-119`` and
   every per-vote status, fire bit, commit event, direct-Verify verdict and per-tx (sum, maj23)
   compared with the sequential oracle.
 
-HBM: 81 keys x 1.70 GB of radix-2^21 tables (138 GB) + the 43 GB base table for the vectors;
+HBM: 83 keys x 1.70 GB of radix-2^21 tables (141 GB) + the 43 GB base table for the vectors;
 43 registry keys (73 GB) + 43 GB for the stream -- one context at a time (the 1e8 gate runs the
 full 111-key set in a process of its own)."""
 import json
@@ -48,7 +51,7 @@ def _golden_cases():
 
 
 def test_shipped_windows_golden_vectors(oracle_lib):
-    """All 339 fixtures at windows 26/21: the split kernel at their own size, the V = 8
+    """All 426 fixtures at windows 26/21: the split kernel at their own size, the V = 8
     work-stealing kernel with the set tiled to 800k items (each item's verdict checked, and the
     oracle's verdict of every distinct triple equal to the recorded one)."""
     import txflow_amd as T
