@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "amino.hpp"
+#include "block_scan.h"
 #include "txv_flow.h"
 
 namespace {
@@ -33,29 +34,6 @@ __device__ __forceinline__ uint64_t upd_value(const UpdateSink& u, uint32_t i, u
   if (i >= n) return 0;
   const uint64_t w = u.cnt[i];
   return (uint32_t)(w >> 32) == stamp ? ((1ull << 32) | (uint32_t)w) : 0ull;
-}
-
-// exclusive scan of x over the 256 threads of a block; *total = block sum
-__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t x, uint64_t* total) {
-  __shared__ uint64_t wsum[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t inc = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((long long)inc, d, 64);
-    if (lane >= d) inc += y;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k < w) before += wsum[k];
-    all += wsum[k];
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - x;
 }
 
 // One wave per set the batch ADDED a vote to (persistent one-wave blocks, as txv_k_tally_cross).

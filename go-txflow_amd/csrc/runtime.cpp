@@ -145,6 +145,14 @@ struct Slot {
   uint64_t u_ticket = 0;           // the ticket that chain belongs to (0: none, e.g. a staged run)
   hipEvent_t u_cons_ev = nullptr;  // a pool's device-to-device staging of the list (pooldev_stage_dev) has
   bool u_cons = false;             // ended: the slot's next list build waits for it
+  // txv_store_sink_enable (submit ring slots): the batch's SaveTx records, encoded behind its tally
+  // (kernels_store.hip): the byte buffer in HBM; the records' offsets, part lengths and set ids, and the
+  // result words (StoreSink::result) in mapped host memory.  u_ticket names the batch for both sinks
+  uint8_t* st_buf = nullptr;
+  StoreRec *h_strec = nullptr, *m_strec = nullptr;
+  uint32_t *h_stres = nullptr, *m_stres = nullptr;
+  bool st_built = false;           // the slot's last chain built records
+  uint32_t st_reading = 0;         // txv_store_records calls copying out of st_buf with no lock held
 };
 
 }  // namespace
@@ -262,6 +270,13 @@ struct txv_ctx {
   uint64_t *d_upd_cnt = nullptr, *d_upd_blk = nullptr;
   uint32_t *d_upd_sid = nullptr, *d_upd_fired = nullptr;
   uint32_t* d_upd_keys = nullptr;   // [upd_cap][8] the list's keys (txv_pool_update_fired on a host-cache pool)
+  // txv_store_sink_enable: bytes and records per slot (0 = off), the record builder's scratch
+  // (StoreSink, txv_flow.h), shared by the slots as the Update list's is, and the read-out's stream
+  uint64_t st_bytes = 0;
+  uint32_t st_recs = 0;
+  uint64_t *d_st_tag = nullptr, *d_st_rlen = nullptr, *d_st_blk = nullptr, *d_st_foff = nullptr;
+  uint32_t* d_st_fired = nullptr;
+  hipStream_t store_stream = nullptr;   // txv_store_records' copies: off the flow and verify streams
   // caller memory registered with txv_host_register (DMA'd without a staging copy)
   std::vector<std::pair<uintptr_t, uint64_t>> registered;
   std::mutex reg_mu;               // `registered` is changed under mu and reg_mu: read under either (the
@@ -537,6 +552,8 @@ int alloc_tally(txv_ctx* c) {
   c->stamp = 0;
   if (c->d_upd_cnt)   // the Update list's columns are tagged with the stamp, which starts over
     HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
+  if (c->d_st_tag)    // and so are the store records'
+    HIP_TRY(c, hipMemsetAsync(c->d_st_tag, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_ctr, 0, sizeof(FlowCounters), c->stream));
   c->seq_next = 0;
   c->n_sets_host = 0;
@@ -1029,12 +1046,21 @@ UpdateSink update_sink(const txv_ctx* c, const Slot& s) {
   return u;
 }
 
+StoreSink store_sink(const txv_ctx* c, const Slot& s) {
+  StoreSink k{};
+  k.cap_bytes = c->st_bytes; k.cap_recs = c->st_recs;
+  k.buf = s.st_buf; k.rec = s.m_strec; k.result = s.m_stres;
+  k.tag = c->d_st_tag; k.rlen = c->d_st_rlen; k.blk = c->d_st_blk; k.fired = c->d_st_fired; k.foff = c->d_st_foff;
+  return k;
+}
+
 // the whole AddVote chain of a staged batch: prep + SignBytes -> K1a/K1b verify (verify
 // stream), set keying -> new ids -> tally -> results into mapped host memory (flow stream)
 int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   Slot& s = c->slots[slot];
   if (!s.staged) { c->err = "slot not staged"; return TXV_ESTATE; }
   if (c->poisoned) { c->err = "a TxFlow capacity was exceeded: txv_reset_flow first"; return TXV_ECAPACITY; }
+  if (s.st_reading) { c->err = "a txv_store_records call is still reading this slot's records"; return TXV_ESTATE; }
   int r;
   if ((r = ensure_park(c))) return r;
   if (c->stamp == 0xFFFFFFFEu) {   // stamps are about to wrap: forget every candidate first
@@ -1042,6 +1068,7 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     HIP_TRY(c, txv_flow_init_cells(&fs0, (uint64_t)c->cfg.max_txs * std::max<uint32_t>(c->n_vals, 1), 0, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_set_stamp, 0, (size_t)c->cfg.max_txs * 4, c->stream));
     if (c->d_upd_cnt) HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
+    if (c->d_st_tag) HIP_TRY(c, hipMemsetAsync(c->d_st_tag, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
     c->stamp = 0;
   }
   s.stamp = ++c->stamp;            // every run of a batch gets a stamp of its own
@@ -1055,6 +1082,7 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   s.run_seq = ++c->run_seq;
   s.u_built = false;               // the slot's earlier list is gone with this run
   s.u_ticket = 0;
+  s.st_built = false;
   const FlowState fs = flow_state(c);
   const FlowBatch fb = flow_batch(c, s);
   // Three compute queues, so that batch k+1 verifies while batch k tallies and nothing but
@@ -1149,6 +1177,12 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     }
     HIP_TRY(c, txv_flow_update_list(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), update_sink(c, s), c->stream));
     s.u_built = true;
+  }
+  // txv_store_sink_enable: the batch's SaveTx records (the same registries; txv_store_records reports
+  // a larger one)
+  if (c->st_recs && s.st_buf && c->n_vals <= TXV_UPD_MAX_VALS) {
+    HIP_TRY(c, txv_flow_store_records(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), store_sink(c, s), c->stream));
+    s.st_built = true;
   }
   HIP_TRY(c, hipEventRecord(s.ev[4], c->stream));
   s.ran = true;
@@ -1538,6 +1572,7 @@ void txv_destroy(txv_ctx* c) {
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
   if (c->vstream) (void)hipStreamSynchronize(c->vstream);
+  if (c->store_stream) (void)hipStreamSynchronize(c->store_stream);
   for (auto& s : c->slots) {
     dfree(s.d_sig); dfree(s.d_msg); dfree(s.d_msg_len); dfree(s.d_val); dfree(s.d_set); dfree(s.d_flags);
     dfree(s.d_status); dfree(s.d_ok); dfree(s.d_pre); dfree(s.d_kbuf); dfree(s.d_rpts); dfree(s.d_order); hfree(s.h_order);
@@ -1550,9 +1585,11 @@ void txv_destroy(txv_ctx* c) {
     dfree(s.d_fh); dfree(s.d_fs); dfree(s.d_fn); dfree(s.d_fo); dfree(s.d_fl); dfree(s.d_arena_th);
     dfree(s.u_sig); dfree(s.u_len); dfree(s.u_size); dfree(s.u_set); hfree(s.h_ures);
     if (s.u_cons_ev) (void)hipEventDestroy(s.u_cons_ev);
+    dfree(s.st_buf); hfree(s.h_strec); hfree(s.h_stres);
     for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
   }
   dfree(c->d_upd_cnt); dfree(c->d_upd_blk); dfree(c->d_upd_sid); dfree(c->d_upd_fired); dfree(c->d_upd_keys);
+  dfree(c->d_st_tag); dfree(c->d_st_rlen); dfree(c->d_st_blk); dfree(c->d_st_fired); dfree(c->d_st_foff);
   dfree(c->d_pubs); dfree(c->d_decode_ok); dfree(c->d_atables); dfree(c->d_vslot); dfree(c->d_addr); dfree(c->d_power);
   dfree(c->d_btable4); dfree(c->d_btable8); dfree(c->d_park); dfree(c->d_wctr); release_base_table(c->device, c->d_btable_wide); c->d_btable = nullptr; dfree(c->d_tmp_pubs); dfree(c->d_tmp_ok); dfree(c->d_tmp_tables); dfree(c->d_tmp_addr);
   dfree(c->d_cells); dfree(c->d_set_cross); dfree(c->d_set_sum);
@@ -1583,6 +1620,7 @@ void txv_destroy(txv_ctx* c) {
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->key_stream) (void)hipStreamDestroy(c->key_stream);
   if (c->vstream) (void)hipStreamDestroy(c->vstream);
+  if (c->store_stream) (void)hipStreamDestroy(c->store_stream);
   delete c;
 }
 
@@ -2356,6 +2394,98 @@ int txv_update_list(txv_ctx* c, uint64_t ticket, uint8_t* sig_out, uint32_t* siz
   if (sig_out) HIP_TRY(c, hipMemcpy(sig_out, s->u_sig, (size_t)n * 64, hipMemcpyDeviceToHost));
   if (size_out) HIP_TRY(c, hipMemcpy(size_out, s->u_size, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (set_out) HIP_TRY(c, hipMemcpy(set_out, s->u_set, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return TXV_OK;
+}
+
+int txv_store_sink_enable(txv_ctx* c, uint64_t max_bytes, uint32_t max_records) {
+  if (!c || (max_bytes != 0) != (max_records != 0)) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
+    if (c->slots[k].st_reading) { c->err = "a txv_store_records call is still reading the sink"; return TXV_ESTATE; }
+  }
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {   // no builder into the old buffers still pending
+    Slot& s = c->slots[k];
+    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
+    s.st_built = false;
+  }
+  c->st_bytes = 0;
+  c->st_recs = 0;
+  const size_t m = max_records, nb = c->cfg.max_batch;
+  const size_t bytes = (size_t)((max_bytes + 15) & ~15ull);
+  int r;
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    Slot& s = c->slots[k];
+    if ((r = dalloc(c, &s.st_buf, bytes)) || (r = halloc_mapped(c, &s.h_strec, &s.m_strec, m)) ||
+        (r = halloc_mapped(c, &s.h_stres, &s.m_stres, m ? 8 : 0)))
+      return r;
+  }
+  if ((r = dalloc(c, &c->d_st_tag, m ? nb : 0)) || (r = dalloc(c, &c->d_st_rlen, m ? nb : 0)) ||
+      (r = dalloc(c, &c->d_st_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0)) || (r = dalloc(c, &c->d_st_fired, m ? nb : 0)) ||
+      (r = dalloc(c, &c->d_st_foff, m ? nb + 1 : 0)))
+    return r;
+  if (!m) return TXV_OK;
+  if (!c->store_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+  HIP_TRY(c, hipMemset(c->d_st_tag, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
+  c->st_bytes = max_bytes & ~15ull;   // records start and end at multiples of 16
+  c->st_recs = max_records;
+  return TXV_OK;
+}
+
+int txv_store_records(txv_ctx* c, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* off_out, uint32_t* lens_out,
+                      uint32_t* set_out, uint32_t rec_cap, uint32_t* n_out, uint64_t* bytes_out) {
+  if (!c) return TXV_EINVAL;
+  if (n_out) *n_out = 0;
+  if (bytes_out) *bytes_out = 0;
+  Slot* sp;
+  uint32_t n;
+  uint64_t bytes;
+  hipEvent_t done;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->st_recs) { c->err = "the store sink is off (txv_store_sink_enable)"; return TXV_ESTATE; }
+    if (!ticket) return TXV_EINVAL;
+    Slot& s = c->slots[(ticket - 1) % kSubmitRing];
+    if (s.u_ticket != ticket) { c->err = "no store records for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
+    if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
+    if (!s.st_built) { c->err = "no store records were built: more than 1024 validators"; return TXV_ESTATE; }
+    uint32_t res[8];
+    memcpy(res, (const void*)s.h_stres, sizeof res);   // written over PCIe before the slot's ev[4]
+    const bool over = res[2] != 0;
+    n = over ? res[1] : res[0];
+    bytes = over ? ((uint64_t)res[7] << 32 | res[6]) : ((uint64_t)res[5] << 32 | res[4]);
+    if (n_out) *n_out = n;
+    if (bytes_out) *bytes_out = bytes;
+    if (over) { c->err = "the batch's store records exceed the sink's max_bytes or max_records"; return TXV_ECAPACITY; }
+    if ((out && cap < bytes) || ((off_out || lens_out || set_out) && rec_cap < n)) {
+      c->err = "txv_store_records: the output arrays are smaller than the records";
+      return TXV_ECAPACITY;
+    }
+    for (uint32_t k = 0; k < n; ++k) {               // (mapped host memory: no copy to wait for)
+      const StoreRec& m = s.h_strec[k];
+      if (off_out) off_out[k] = m.off;
+      if (lens_out) memcpy(lens_out + 4 * (size_t)k, m.len, 16);
+      if (set_out) set_out[k] = m.set;
+    }
+    if (!out || !bytes) return TXV_OK;
+    ++s.st_reading;                                    // the slot's next submit is refused meanwhile
+    sp = &s;
+    done = s.ev[4];
+  }
+  // the copy with no lock held: only the bytes used, on the read-out's own stream behind the
+  // ticket's completion event (already reached: the ticket was waited for), so nothing in flight on
+  // the flow or verify stream is waited for
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipStreamWaitEvent(c->store_stream, done, 0);
+  if (he == hipSuccess) he = hipMemcpyAsync(out, sp->st_buf, bytes, hipMemcpyDeviceToHost, c->store_stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->store_stream);
+  std::lock_guard<std::mutex> g(c->mu);
+  --sp->st_reading;
+  if (he != hipSuccess) {
+    c->err = std::string("txv_store_records: ") + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
   return TXV_OK;
 }
 

@@ -223,6 +223,34 @@ struct UpdateSink {
   uint32_t* fired;                // [max_batch][2] (set id, first entry) of the fired sets in list order
 };
 
+// TxStore.SaveTx's records for one batch, amino-encoded on the device (kernels_store.hip): one
+// record per set that fired in the batch, in the order of each set's last fired vote, built from the
+// set's accepted votes as of the end of the batch -- txflow/service.go:216-218's
+// `txStore.SaveTx(set)` (tx/store.go:83-117) once per set and batch: both db.Set keys depend on the
+// TxHash alone, so the last write wins.
+struct StoreRec {                 // 32 B, mapped host memory
+  uint64_t off;                   // byte offset of the record in the sink (a multiple of 16)
+  uint32_t len[4];                // "H:%X" | TxVoteSet bytes | "C:%X" | Commit bytes, back to back
+  uint32_t set;                   // set id
+  uint32_t pad0;
+};
+struct StoreSink {
+  uint64_t cap_bytes;             // bytes the sink holds
+  uint32_t cap_recs;              // records the sink describes
+  uint32_t pad0;
+  uint8_t* buf;                   // [cap_bytes] the records, zero padded to 16-byte offsets
+  StoreRec* rec;                  // [cap_recs] mapped host memory
+  uint32_t* result;               // mapped host memory: records written, records needed, overflow, 0,
+                                  // bytes written (u64), bytes needed (u64)
+  // scratch shared by every slot of the context (the builders run in flow-stream order)
+  uint64_t* tag;                  // [max_batch] (stamp << 32 | set id) of the set whose last fired vote
+                                  // arrived at this index (stamp-tagged: never cleared)
+  uint64_t* rlen;                 // [max_batch] that set's record length
+  uint64_t* blk;                  // [ceil(max_batch / 1024) + 1][2] scan blocks: (records, padded bytes)
+  uint32_t* fired;                // [max_batch] set ids of the records in list order
+  uint64_t* foff;                 // [max_batch + 1] their byte offsets; foff[records] = the bytes needed
+};
+
 extern "C" {
 // the whole AddVote chain of one batch except SignBytes and verify, on two streams:
 // prep (pre-checks, validator lookup, signature transpose, SignBytes lengths: everything the
@@ -241,6 +269,9 @@ const uint32_t* txv_flow_n_stamped(const FlowState* fs, const FlowBatch* b, uint
 // after the tally, on the same stream: the batch's Update list into the sink (kernels_update.hip)
 hipError_t txv_flow_update_list(const FlowState* fs, const FlowBatch* b, const uint32_t* n_stamped, UpdateSink u,
                                 hipStream_t st);
+// the same place, when the store sink is on: the batch's SaveTx records (kernels_store.hip)
+hipError_t txv_flow_store_records(const FlowState* fs, const FlowBatch* b, const uint32_t* n_stamped, StoreSink k,
+                                  hipStream_t st);
 // forget every TxVoteSet (keep_ids = 0) or empty them keeping their ids (keep_ids = 1)
 hipError_t txv_flow_reset(const FlowState* fs, int keep_ids, hipStream_t st);
 // cells of the first `cells` (set, validator) pairs: every candidate forgotten (cand = ~0), and

@@ -66,6 +66,18 @@ class UpdateListError(TxvInfraError):
         self.n = n
 
 
+class StoreRecordsError(TxvInfraError):
+    """Context.store_records: no records to read (rc = E_STATE: sink off, ticket not waited, slot
+    reused) or the batch's records overflowed the sink (rc = E_CAPACITY, n = the records and
+    nbytes = the bytes it needs)"""
+
+    def __init__(self, what, rc, n, nbytes, msg):
+        super().__init__(f"{what} failed ({rc}): {msg}")
+        self.rc = rc
+        self.n = n
+        self.nbytes = nbytes
+
+
 class TxvCapacityError(TxvInfraError):
     """Context.route_wait / route_admitted / route_checked: a rank's buffer would not fit its stride
     (TXV_ECAPACITY).  metas = every rank's txv_route_meta: the refused ones have reserved = 1, their
@@ -230,6 +242,9 @@ def lib():
             "txv_submit_routed": ([vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "txv_update_sink_enable": ([vp, u32], ctypes.c_int),
             "txv_update_list": ([vp, ctypes.c_uint64, vp, vp, vp, u32, ctypes.POINTER(u32)], ctypes.c_int),
+            "txv_store_sink_enable": ([vp, ctypes.c_uint64, u32], ctypes.c_int),
+            "txv_store_records": ([vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, u32, ctypes.POINTER(u32),
+                                   ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "txv_pool_update_fired": ([vp, vp, i64, ctypes.c_uint64], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
@@ -260,7 +275,8 @@ EXPORTED_SYMBOLS = [
     "txv_ingest_decode", "txv_ingest_admit", "txv_route_bytes", "txv_route_admitted", "txv_route_checked", "txv_route_pack_host",
     "txv_route_view", "txv_submit_routed", "txv_route_submit_admitted", "txv_route_submit_checked", "txv_route_wait",
     "txv_ingest_admit_submit", "txv_ingest_admit_finish",
-    "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired"]
+    "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired",
+    "txv_store_sink_enable", "txv_store_records"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -756,6 +772,42 @@ class Context:
             if rc < 0:
                 raise UpdateListError("txv_update_list", rc, n.value, lib().txv_last_error(self._h).decode())
         return sig, size, sets
+
+    def enable_store_sink(self, max_bytes: int, max_records: int):
+        """txv_store_sink_enable: every submitted batch leaves its TxStore.SaveTx records (one per set
+        it fired, by last fired vote, amino-encoded on the GPU) in HBM, up to max_bytes bytes and
+        max_records records per batch; (0, 0) turns it off"""
+        self._chk(lib().txv_store_sink_enable(self._h, max_bytes, max_records), "txv_store_sink_enable")
+
+    def store_records_raw(self, ticket: int, out: np.ndarray | None = None):
+        """txv_store_records for a waited ticket: (buffer u8, offsets [n] u64, part lengths [n, 4]
+        u32, set ids [n] u32); `out` (u8, e.g. pinned) receives the buffer when it is large enough.
+        StoreRecordsError (rc = TXV_ESTATE / TXV_ECAPACITY) when there are no records to read."""
+        n = ctypes.c_uint32(); nb = ctypes.c_uint64()
+        rc = lib().txv_store_records(self._h, ticket, None, 0, None, None, None, 0, ctypes.byref(n), ctypes.byref(nb))
+        if rc < 0:
+            raise StoreRecordsError("txv_store_records", rc, n.value, nb.value, lib().txv_last_error(self._h).decode())
+        k, nbytes = n.value, nb.value
+        buf = out if out is not None and out.nbytes >= nbytes else np.zeros(max(nbytes, 1), np.uint8)
+        off = np.zeros(max(k, 1), np.uint64); lens = np.zeros((max(k, 1), 4), np.uint32); sets = np.zeros(max(k, 1), np.uint32)
+        rc = lib().txv_store_records(self._h, ticket, buf.ctypes.data, buf.nbytes, off.ctypes.data, lens.ctypes.data,
+                                     sets.ctypes.data, k, ctypes.byref(n), ctypes.byref(nb))
+        if rc < 0:
+            raise StoreRecordsError("txv_store_records", rc, n.value, nb.value, lib().txv_last_error(self._h).decode())
+        return buf[:nbytes], off[:k], lens[:k], sets[:k]
+
+    def store_records(self, ticket: int):
+        """the batch's SaveTx records in write order: [(set id, H-key, TxVoteSet bytes, C-key, Commit
+        bytes)], i.e. db.Set(H-key, TxVoteSet bytes) and db.Set(C-key, Commit bytes) per record"""
+        buf, off, lens, sets = self.store_records_raw(ticket)
+        raw, recs = buf.tobytes(), []
+        for o, ln, sid in zip(off.tolist(), lens.tolist(), sets.tolist()):
+            parts = []
+            for L in ln:
+                parts.append(raw[o:o + L])
+                o += L
+            recs.append((sid, *parts))
+        return recs
 
     def get_votes(self, txhash: bytes):
         """TxVoteSet.GetVotes: [(validator index, vote sequence number, signature bytes)] in

@@ -256,6 +256,39 @@ int txv_update_sink_enable(txv_ctx* ctx, uint32_t max_entries);
 int txv_update_list(txv_ctx* ctx, uint64_t ticket, uint8_t* sig_out, uint32_t* size_out, uint32_t* set_out,
                     uint32_t cap, uint32_t* n_out);
 
+/* TxStore.SaveTx's records built on the device (txflow/service.go:216-218: the commit block runs
+ * txStore.SaveTx(set) for every fired vote; tx/store.go:83-117: db.Set("H:%X", TxVoteSet bytes) and
+ * db.Set("C:%X", MakeCommit bytes)).  Both keys depend on the TxHash alone, so the last write wins:
+ * every ADDED vote of a committed set fires, so a set's last fired vote of a batch is its last ADDED
+ * vote of that batch, and the record written there is the one built from the set's accepted votes
+ * as of the end of the batch.  With the sink enabled, every batch of the submit ring
+ * (txv_submit_votes, txv_submit_checked, txv_submit_routed, and txv_add_votes through them) leaves,
+ * behind its tally, one record per set that fired in it, ordered by the arrival index of each set's
+ * last fired vote: writing them in that order leaves a key-value store as the reference's per-vote
+ * cadence does.  (The height descriptor SaveTx also writes is the caller's state.LastBlockHeight.)
+ * A record's bytes are those of txv_save_tx_bytes (CommitSigs in validator-index order), encoded
+ * on the GPU; both sinks may be on at once.
+ * txv_store_sink_enable: per-slot buffers of max_bytes bytes and max_records records for the
+ *   four-slot ring; (0, 0) disables and frees them (the default: no record is built).  Waits for
+ *   the chains in flight; TXV_ESTATE while a submitted batch has not been waited for.
+ * txv_store_records: the records of the batch `ticket` names, readable from the return of
+ *   txv_wait_votes(ticket) until the slot's next batch is submitted (four submits later; a submit
+ *   into the slot while a read-out is copying fails with TXV_ESTATE).  out = the buffer as built:
+ *   record k at off_out[k], a multiple of 16, its four parts -- "H:%X" key, TxVoteSet bytes, "C:%X"
+ *   key, Commit bytes -- back to back with the lengths lens_out[4k .. 4k+3], zero padding up to the
+ *   next record; set_out[k] = its set id (tx_index of the commit events).  Any output may be NULL;
+ *   *n_out = records, *bytes_out = buffer bytes.  Only the bytes used are copied, on a stream of the
+ *   read-out's own and without the context's lock, so batches in flight are not stalled.
+ *   TXV_ESTATE when the sink is off, the ticket has not been waited for, its slot was reused, or the
+ *   registry has more than 1024 validators (no record is built then); TXV_ECAPACITY when the batch
+ *   overflowed the sink (*n_out, *bytes_out = what it needs; the batch's TxFlow results are not
+ *   affected and the TxFlow is not poisoned) or `cap` / `rec_cap` is too small (*n_out, *bytes_out =
+ *   the records' counts; nothing written). */
+int txv_store_sink_enable(txv_ctx* ctx, uint64_t max_bytes, uint32_t max_records);
+int txv_store_records(txv_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* off_out,
+                      uint32_t* lens_out, uint32_t* set_out, uint32_t rec_cap, uint32_t* n_out,
+                      uint64_t* bytes_out);
+
 /* Tally readers for the TxVoteSet of txhash.  Returns 1 if the set exists, 0 if not. */
 int txv_query_tx(txv_ctx* ctx, const uint8_t* txhash, uint32_t len, int64_t* sum, uint8_t* maj23);
 /* the same for n TxHashes (txhash + off[i], len[i] bytes); any output may be NULL; txkey_out
