@@ -153,6 +153,14 @@ struct Slot {
   uint32_t *h_stres = nullptr, *m_stres = nullptr;
   bool st_built = false;           // the slot's last chain built records
   uint32_t st_reading = 0;         // txv_store_records calls copying out of st_buf with no lock held
+  // txv_gossip_sink_enable (submit ring slots): the batch's TxVoteMessages, encoded from its raw columns
+  // before its tally (kernels_gossip.hip): bytes and descriptors in HBM, the result words
+  // (GossipSink::result) in mapped host memory, and the read-out's pinned copy of the descriptors
+  uint8_t* g_buf = nullptr;
+  GossipDesc *g_desc = nullptr, *h_gdesc = nullptr;
+  uint32_t *h_gres = nullptr, *m_gres = nullptr;
+  bool g_built = false;            // the slot's last chain built messages
+  uint32_t g_reading = 0;          // a txv_gossip_msgs call is copying out of g_buf / g_desc with no lock held
 };
 
 }  // namespace
@@ -277,6 +285,12 @@ struct txv_ctx {
   uint64_t *d_st_tag = nullptr, *d_st_rlen = nullptr, *d_st_blk = nullptr, *d_st_foff = nullptr;
   uint32_t* d_st_fired = nullptr;
   hipStream_t store_stream = nullptr;   // txv_store_records' copies: off the flow and verify streams
+  // txv_gossip_sink_enable: bytes and entries per slot (0 = off), the TxVoteMessage amino prefix, the
+  // chain's scratch (GossipSink, txv_flow.h), shared by the slots, and the read-out's stream
+  uint64_t g_bytes = 0;
+  uint32_t g_msgs = 0, g_prefix = 0;
+  uint64_t *d_g_ent = nullptr, *d_g_lay = nullptr, *d_g_blk = nullptr;
+  hipStream_t gossip_stream = nullptr;  // txv_gossip_msgs' copies
   // caller memory registered with txv_host_register (DMA'd without a staging copy)
   std::vector<std::pair<uintptr_t, uint64_t>> registered;
   std::mutex reg_mu;               // `registered` is changed under mu and reg_mu: read under either (the
@@ -924,7 +938,9 @@ int stage_add(txv_ctx* c, uint32_t slot, const txv_votes* v, bool route = false)
   add((uniform >> kUHL & 1) ? nullptr : v->txhash_len, s.h_fl, s.d_fl, 4);
   // ValidatorSet.GetByAddress on the pack threads (the device's table, host_pack.hpp AddrTable):
   // a 2-byte code per vote crosses PCIe instead of the 20-byte address and its length
-  const bool host_val = !route && (c->host_val == 1 || (c->host_val < 0 && n >= kHostValMin)) && v->addr &&
+  // (not while the gossip sink is on: its messages carry the address bytes, which must be in HBM,
+  // and the code loses an unknown validator's address)
+  const bool host_val = !route && !c->g_msgs && (c->host_val == 1 || (c->host_val < 0 && n >= kHostValMin)) && v->addr &&
                         v->addr_len && c->n_vals < kVcodeEmpty;
   s.host_val = host_val;
   if (!host_val) {
@@ -1054,6 +1070,14 @@ StoreSink store_sink(const txv_ctx* c, const Slot& s) {
   return k;
 }
 
+GossipSink gossip_sink(const txv_ctx* c, const Slot& s) {
+  GossipSink k{};
+  k.cap_bytes = c->g_bytes; k.cap_msgs = c->g_msgs; k.prefix = c->g_prefix;
+  k.buf = s.g_buf; k.desc = s.g_desc; k.result = s.m_gres;
+  k.ent = c->d_g_ent; k.lay = c->d_g_lay; k.blk = c->d_g_blk;
+  return k;
+}
+
 // the whole AddVote chain of a staged batch: prep + SignBytes -> K1a/K1b verify (verify
 // stream), set keying -> new ids -> tally -> results into mapped host memory (flow stream)
 int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
@@ -1061,6 +1085,7 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   if (!s.staged) { c->err = "slot not staged"; return TXV_ESTATE; }
   if (c->poisoned) { c->err = "a TxFlow capacity was exceeded: txv_reset_flow first"; return TXV_ECAPACITY; }
   if (s.st_reading) { c->err = "a txv_store_records call is still reading this slot's records"; return TXV_ESTATE; }
+  if (s.g_reading) { c->err = "a txv_gossip_msgs call is still reading this slot's messages"; return TXV_ESTATE; }
   int r;
   if ((r = ensure_park(c))) return r;
   if (c->stamp == 0xFFFFFFFEu) {   // stamps are about to wrap: forget every candidate first
@@ -1083,6 +1108,7 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   s.u_built = false;               // the slot's earlier list is gone with this run
   s.u_ticket = 0;
   s.st_built = false;
+  s.g_built = false;
   const FlowState fs = flow_state(c);
   const FlowBatch fb = flow_batch(c, s);
   // Three compute queues, so that batch k+1 verifies while batch k tallies and nothing but
@@ -1152,6 +1178,14 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   HIP_TRY(c, txv_flow_route(&fs, &fb, c->stream));
   HIP_TRY(c, txv_flow_new_ids(&fs, &fb, c->stream));
   HIP_TRY(c, hipEventRecord(s.ev[6], c->stream));
+  // txv_gossip_sink_enable: the batch's TxVoteMessages, here, where the flow stream would idle until
+  // this batch's verify ends.  The chain reads only the raw columns, which the stream's wait for
+  // ev[3] above covers (uploads, fills, a CheckTx batch's signatures and nil column) and nothing
+  // rewrites before the slot's next staging (which waits for ev[4])
+  if (c->g_msgs && s.g_buf && !s.host_val) {
+    HIP_TRY(c, txv_flow_gossip_msgs(&fb, gossip_sink(c, s), c->stream));
+    s.g_built = true;
+  }
   // set ids in use after this batch: at most those known at the newest fetched run + one per
   // vote of every run not fetched yet (a bound for the touched-set scan).  A slot run again
   // before it was fetched keeps its earlier run's votes counted too: that run's sets only show
@@ -1573,6 +1607,7 @@ void txv_destroy(txv_ctx* c) {
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
   if (c->vstream) (void)hipStreamSynchronize(c->vstream);
   if (c->store_stream) (void)hipStreamSynchronize(c->store_stream);
+  if (c->gossip_stream) (void)hipStreamSynchronize(c->gossip_stream);
   for (auto& s : c->slots) {
     dfree(s.d_sig); dfree(s.d_msg); dfree(s.d_msg_len); dfree(s.d_val); dfree(s.d_set); dfree(s.d_flags);
     dfree(s.d_status); dfree(s.d_ok); dfree(s.d_pre); dfree(s.d_kbuf); dfree(s.d_rpts); dfree(s.d_order); hfree(s.h_order);
@@ -1586,10 +1621,12 @@ void txv_destroy(txv_ctx* c) {
     dfree(s.u_sig); dfree(s.u_len); dfree(s.u_size); dfree(s.u_set); hfree(s.h_ures);
     if (s.u_cons_ev) (void)hipEventDestroy(s.u_cons_ev);
     dfree(s.st_buf); hfree(s.h_strec); hfree(s.h_stres);
+    dfree(s.g_buf); dfree(s.g_desc); hfree(s.h_gdesc); hfree(s.h_gres);
     for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
   }
   dfree(c->d_upd_cnt); dfree(c->d_upd_blk); dfree(c->d_upd_sid); dfree(c->d_upd_fired); dfree(c->d_upd_keys);
   dfree(c->d_st_tag); dfree(c->d_st_rlen); dfree(c->d_st_blk); dfree(c->d_st_fired); dfree(c->d_st_foff);
+  dfree(c->d_g_ent); dfree(c->d_g_lay); dfree(c->d_g_blk);
   dfree(c->d_pubs); dfree(c->d_decode_ok); dfree(c->d_atables); dfree(c->d_vslot); dfree(c->d_addr); dfree(c->d_power);
   dfree(c->d_btable4); dfree(c->d_btable8); dfree(c->d_park); dfree(c->d_wctr); release_base_table(c->device, c->d_btable_wide); c->d_btable = nullptr; dfree(c->d_tmp_pubs); dfree(c->d_tmp_ok); dfree(c->d_tmp_tables); dfree(c->d_tmp_addr);
   dfree(c->d_cells); dfree(c->d_set_cross); dfree(c->d_set_sum);
@@ -1621,6 +1658,7 @@ void txv_destroy(txv_ctx* c) {
   if (c->key_stream) (void)hipStreamDestroy(c->key_stream);
   if (c->vstream) (void)hipStreamDestroy(c->vstream);
   if (c->store_stream) (void)hipStreamDestroy(c->store_stream);
+  if (c->gossip_stream) (void)hipStreamDestroy(c->gossip_stream);
   delete c;
 }
 
@@ -2484,6 +2522,110 @@ int txv_store_records(txv_ctx* c, uint64_t ticket, uint8_t* out, uint64_t cap, u
   --sp->st_reading;
   if (he != hipSuccess) {
     c->err = std::string("txv_store_records: ") + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
+  return TXV_OK;
+}
+
+int txv_gossip_sink_enable(txv_ctx* c, uint64_t max_bytes, uint32_t max_msgs) {
+  if (!c || (max_bytes != 0) != (max_msgs != 0)) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
+    if (c->slots[k].g_reading) { c->err = "a txv_gossip_msgs call is still reading the sink"; return TXV_ESTATE; }
+  }
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {   // no chain into the old buffers still pending
+    Slot& s = c->slots[k];
+    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
+    s.g_built = false;
+  }
+  c->g_bytes = 0;
+  c->g_msgs = 0;
+  const size_t m = max_msgs, nb = c->cfg.max_batch;
+  const size_t bytes = (size_t)((max_bytes + 15) & ~15ull);
+  int r;
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {
+    Slot& s = c->slots[k];
+    if ((r = dalloc(c, &s.g_buf, bytes)) || (r = dalloc(c, &s.g_desc, m)) || (r = halloc(c, &s.h_gdesc, m)) ||
+        (r = halloc_mapped(c, &s.h_gres, &s.m_gres, m ? 8 : 0)))
+      return r;
+  }
+  if ((r = dalloc(c, &c->d_g_ent, m ? nb : 0)) || (r = dalloc(c, &c->d_g_lay, m ? nb : 0)) || (r = dalloc(c, &c->d_g_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0))) return r;
+  if (!m) return TXV_OK;
+  if (!c->gossip_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->gossip_stream, hipStreamNonBlocking));
+  // amino nameToDisfix("tendermint/txvotepool/TxVoteMessage"): SHA-256 of the registered name, zero
+  // bytes skipped, 3 disambiguation bytes, zero bytes skipped, 4 prefix bytes (as txv_encode_msgs)
+  static const char name[] = "tendermint/txvotepool/TxVoteMessage";
+  uint8_t h[32];
+  txv_sha256_bytes(reinterpret_cast<const uint8_t*>(name), sizeof name - 1, h);
+  int i = 0;
+  while (h[i] == 0) ++i;
+  i += 3;
+  while (h[i] == 0) ++i;
+  c->g_prefix = le32(h + i);
+  c->g_bytes = max_bytes & ~15ull;   // messages start and end at multiples of 16
+  c->g_msgs = max_msgs;
+  return TXV_OK;
+}
+
+int txv_gossip_msgs(txv_ctx* c, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* off_out, uint32_t* len_out,
+                    uint32_t* idx_out, uint8_t* flag_out, uint32_t msg_cap, uint32_t* n_out, uint64_t* bytes_out) {
+  if (!c) return TXV_EINVAL;
+  if (n_out) *n_out = 0;
+  if (bytes_out) *bytes_out = 0;
+  Slot* sp;
+  uint32_t n;
+  uint64_t bytes;
+  hipEvent_t done;
+  const bool want_desc = off_out || len_out || idx_out || flag_out;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->g_msgs) { c->err = "the gossip sink is off (txv_gossip_sink_enable)"; return TXV_ESTATE; }
+    if (!ticket) return TXV_EINVAL;
+    Slot& s = c->slots[(ticket - 1) % kSubmitRing];
+    if (s.u_ticket != ticket) { c->err = "no gossip messages for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
+    if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
+    if (!s.g_built) { c->err = "no gossip messages were built for this batch: it was staged (txv_stage) with the host validator lookup before the sink was enabled"; return TXV_ESTATE; }
+    uint32_t res[8];
+    memcpy(res, (const void*)s.h_gres, sizeof res);   // written over PCIe before the slot's ev[4]
+    n = res[0];
+    bytes = (uint64_t)res[5] << 32 | res[4];
+    if (n_out) *n_out = n;
+    if (bytes_out) *bytes_out = bytes;
+    if (res[1]) { c->err = "the batch's gossip messages exceed the sink's max_bytes or max_msgs"; return TXV_ECAPACITY; }
+    if ((out && cap < bytes) || (want_desc && msg_cap < n)) {
+      c->err = "txv_gossip_msgs: the output arrays are smaller than the messages";
+      return TXV_ECAPACITY;
+    }
+    if ((!out || !bytes) && (!want_desc || !n)) return TXV_OK;
+    // one read-out per slot at a time: the descriptors pass through the slot's pinned buffer
+    if (s.g_reading) { c->err = "another txv_gossip_msgs call is reading this slot"; return TXV_ESTATE; }
+    ++s.g_reading;                                     // the slot's next submit is refused meanwhile
+    sp = &s;
+    done = s.ev[4];
+  }
+  // the copies with no lock held: only the bytes and descriptors used, on the read-out's own stream
+  // behind the ticket's completion event (already reached: the ticket was waited for), so nothing in
+  // flight on the flow or verify stream is waited for
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipStreamWaitEvent(c->gossip_stream, done, 0);
+  if (he == hipSuccess && want_desc && n)
+    he = hipMemcpyAsync(sp->h_gdesc, sp->g_desc, (size_t)n * sizeof(GossipDesc), hipMemcpyDeviceToHost, c->gossip_stream);
+  if (he == hipSuccess && out && bytes) he = hipMemcpyAsync(out, sp->g_buf, bytes, hipMemcpyDeviceToHost, c->gossip_stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->gossip_stream);
+  if (he == hipSuccess && want_desc)
+    for (uint32_t k = 0; k < n; ++k) {
+      const GossipDesc d = sp->h_gdesc[k];
+      if (off_out) off_out[k] = (uint64_t)d.off_hi << 32 | (d.off_lo & ~15u);
+      if (len_out) len_out[k] = d.len;
+      if (idx_out) idx_out[k] = d.idx;
+      if (flag_out) flag_out[k] = (uint8_t)(d.off_lo & 15u);
+    }
+  std::lock_guard<std::mutex> g(c->mu);
+  --sp->g_reading;
+  if (he != hipSuccess) {
+    c->err = std::string("txv_gossip_msgs: ") + hipGetErrorString(he);
     return TXV_EDEVICE;
   }
   return TXV_OK;

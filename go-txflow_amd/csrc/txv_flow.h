@@ -251,7 +251,33 @@ struct StoreSink {
   uint64_t* foff;                 // [max_batch + 1] their byte offsets; foff[records] = the bytes needed
 };
 
+// The gossip sink (kernels_gossip.hip): the TxVoteMessage bytes of a batch's non-nil votes, in
+// arrival order, amino-encoded on the device from the slot's raw columns -- what
+// broadcastTxRoutine (txvotepool/reactor.go:198-265) sends for every pool entry.
+struct GossipDesc {               // 16 B, HBM (copied at read-out)
+  uint32_t off_lo;                // byte offset of the message in the sink (a multiple of 16) | flag (low 4 bits)
+  uint32_t off_hi;
+  uint32_t len;                   // message bytes (0 when flagged)
+  uint32_t idx;                   // the vote's index in the batch
+};
+struct GossipSink {
+  uint64_t cap_bytes;             // bytes the sink holds
+  uint32_t cap_msgs;              // entries the sink describes
+  uint32_t prefix;                // the 4 amino prefix bytes of TxVoteMessage (little-endian word)
+  uint8_t* buf;                   // [cap_bytes] the messages, zero padded to 16-byte offsets
+  GossipDesc* desc;               // [cap_msgs]
+  uint32_t* result;               // mapped host memory: entries, overflow, 0, 0, bytes needed (u64), 0, 0
+  // scratch shared by every slot of the context (the chains run in flow-stream order); every word
+  // a batch reads it wrote itself, so nothing is tagged or cleared
+  uint64_t* ent;                  // [max_batch] listed << 63 | flag << 32 | message length
+  uint64_t* lay;                  // [max_batch] an encodable entry's field lengths (gossip_dev.h msg_measure)
+  uint64_t* blk;                  // [ceil(max_batch / 1024) + 1][2] scan blocks: (entries, padded bytes)
+};
+
 extern "C" {
+// the gossip sink's chain for one batch (flow stream, between the new set ids and the tally): it
+// reads only the raw columns of b
+hipError_t txv_flow_gossip_msgs(const FlowBatch* b, GossipSink k, hipStream_t st);
 // the whole AddVote chain of one batch except SignBytes and verify, on two streams:
 // prep (pre-checks, validator lookup, signature transpose, SignBytes lengths: everything the
 // verify kernels read, nothing keyed by the TxFlow) runs on the verify stream ...

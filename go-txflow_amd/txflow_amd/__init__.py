@@ -78,6 +78,21 @@ class StoreRecordsError(TxvInfraError):
         self.nbytes = nbytes
 
 
+GOSSIP_OK, GOSSIP_HOST, GOSSIP_UNENCODABLE = range(3)   # TXV_GOSSIP_*
+
+
+class GossipMsgsError(TxvInfraError):
+    """Context.gossip_msgs: no messages to read (rc = E_STATE: sink off, ticket not waited, slot
+    reused) or the batch's messages overflowed the sink (rc = E_CAPACITY, n = the entries and
+    nbytes = the bytes it needs)"""
+
+    def __init__(self, what, rc, n, nbytes, msg):
+        super().__init__(f"{what} failed ({rc}): {msg}")
+        self.rc = rc
+        self.n = n
+        self.nbytes = nbytes
+
+
 class TxvCapacityError(TxvInfraError):
     """Context.route_wait / route_admitted / route_checked: a rank's buffer would not fit its stride
     (TXV_ECAPACITY).  metas = every rank's txv_route_meta: the refused ones have reserved = 1, their
@@ -246,6 +261,9 @@ def lib():
             "txv_store_records": ([vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, u32, ctypes.POINTER(u32),
                                    ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "txv_pool_update_fired": ([vp, vp, i64, ctypes.c_uint64], ctypes.c_int),
+            "txv_gossip_sink_enable": ([vp, ctypes.c_uint64, u32], ctypes.c_int),
+            "txv_gossip_msgs": ([vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, vp, u32, ctypes.POINTER(u32),
+                                 ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -276,7 +294,8 @@ EXPORTED_SYMBOLS = [
     "txv_route_view", "txv_submit_routed", "txv_route_submit_admitted", "txv_route_submit_checked", "txv_route_wait",
     "txv_ingest_admit_submit", "txv_ingest_admit_finish",
     "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired",
-    "txv_store_sink_enable", "txv_store_records"]
+    "txv_store_sink_enable", "txv_store_records",
+    "txv_gossip_sink_enable", "txv_gossip_msgs"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -808,6 +827,32 @@ class Context:
                 o += L
             recs.append((sid, *parts))
         return recs
+
+    def enable_gossip_sink(self, max_bytes: int, max_msgs: int):
+        """txv_gossip_sink_enable: every submitted batch leaves the TxVoteMessage bytes of its non-nil
+        votes (for submit_checked: the votes the pool admitted), in arrival order, amino-encoded on
+        the GPU, in HBM, up to max_bytes bytes and max_msgs entries per batch; (0, 0) turns it off"""
+        self._chk(lib().txv_gossip_sink_enable(self._h, max_bytes, max_msgs), "txv_gossip_sink_enable")
+
+    def gossip_msgs(self, ticket: int, out: np.ndarray | None = None):
+        """txv_gossip_msgs for a waited ticket: (WireBatch over the buffer as built -- message k at
+        off[k], a multiple of 16, len[k] bytes, 0 when flagged --, idx [n] u32 = each entry's vote
+        index in the batch, flag [n] u8 = GOSSIP_OK / GOSSIP_HOST / GOSSIP_UNENCODABLE); `out` (u8,
+        e.g. pinned) receives the buffer when it is large enough.  GossipMsgsError (rc = TXV_ESTATE
+        / TXV_ECAPACITY) when there are no messages to read."""
+        n = ctypes.c_uint32(); nb = ctypes.c_uint64()
+        rc = lib().txv_gossip_msgs(self._h, ticket, None, 0, None, None, None, None, 0, ctypes.byref(n), ctypes.byref(nb))
+        if rc < 0:
+            raise GossipMsgsError("txv_gossip_msgs", rc, n.value, nb.value, lib().txv_last_error(self._h).decode())
+        k, nbytes = n.value, nb.value
+        buf = out if out is not None and out.nbytes >= nbytes else np.zeros(max(nbytes, 1), np.uint8)
+        off = np.zeros(max(k, 1), np.uint64); ln = np.zeros(max(k, 1), np.uint32)
+        idx = np.zeros(max(k, 1), np.uint32); flag = np.zeros(max(k, 1), np.uint8)
+        rc = lib().txv_gossip_msgs(self._h, ticket, buf.ctypes.data, buf.nbytes, off.ctypes.data, ln.ctypes.data,
+                                   idx.ctypes.data, flag.ctypes.data, k, ctypes.byref(n), ctypes.byref(nb))
+        if rc < 0:
+            raise GossipMsgsError("txv_gossip_msgs", rc, n.value, nb.value, lib().txv_last_error(self._h).decode())
+        return WireBatch(wire=buf[:nbytes], off=off[:k], length=ln[:k]), idx[:k], flag[:k]
 
     def get_votes(self, txhash: bytes):
         """TxVoteSet.GetVotes: [(validator index, vote sequence number, signature bytes)] in

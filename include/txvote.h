@@ -34,6 +34,8 @@
  *                         txvotepool/reactor.go:278-291 (codec: reactor.go:273-276, codec.go)
  *   txv_encode_msgs    <- cdc.MustMarshalBinaryBare(&TxVoteMessage{tx}) in broadcastTxRoutine
  *                         txvotepool/reactor.go:248 (the sending side of the same wire format)
+ *   txv_gossip_msgs    <- the messages broadcastTxRoutine sends for a batch's admitted votes,
+ *                         txvotepool/reactor.go:198-265, encoded on the device per batch
  *   txv_pool_receive   <- func (txR *Reactor) Receive(chID byte, src p2p.Peer, msgBytes []byte)
  *                         txvotepool/reactor.go:170-190 (decodeMsg + CheckTxWithInfo per message)
  *   txv_route_admitted / txv_submit_routed <- the Receive -> CheckTxWithInfo -> TryAddVote hand-off
@@ -288,6 +290,53 @@ int txv_store_sink_enable(txv_ctx* ctx, uint64_t max_bytes, uint32_t max_records
 int txv_store_records(txv_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* off_out,
                       uint32_t* lens_out, uint32_t* set_out, uint32_t rec_cap, uint32_t* n_out,
                       uint64_t* bytes_out);
+
+/* The gossip sink: the sending side of CheckTx admission, built on the device.
+ * broadcastTxRoutine (txvotepool/reactor.go:198-265) walks the pool list in order, sends
+ * cdc.MustMarshalBinaryBare(&TxVoteMessage{Tx}) (:247-248) for every entry and skips the peer that
+ * sent the vote itself (:245).  With the sink enabled, every batch of the submit ring
+ * (txv_submit_votes, txv_submit_checked, txv_submit_routed, and txv_add_votes through them) leaves
+ * one entry per non-nil vote, in arrival order, and the entries' TxVoteMessage bytes -- those of
+ * txv_encode_msgs, amino-encoded on the GPU from the batch's columns in HBM -- in one buffer.  For
+ * txv_submit_checked the non-nil votes are exactly those the pool admitted, and arrival order is
+ * the order broadcastTxRoutine walks the pool list.  The chain runs on the flow stream before the
+ * batch's tally, while that stream waits for the batch's verify; it touches no TxFlow state.  The
+ * send itself, and the per-entry sender sets (txvotepool.go:213-250), stay the caller's.  The
+ * Update, store and gossip sinks may all be on at once.
+ * Entry flags:
+ *   TXV_GOSSIP_OK           the message is in the buffer
+ *   TXV_GOSSIP_HOST         sig_len > 64 or addr_len > 20 (the columns hold only the first 64 / 20
+ *                           bytes), or a message of 4 GiB or more: no bytes in the buffer (len 0);
+ *                           the caller encodes this vote with txv_encode_msgs
+ *   TXV_GOSSIP_UNENCODABLE  amino rejects the time: the reference's MustMarshalBinaryBare panics;
+ *                           no bytes (len 0)
+ * txv_gossip_sink_enable: per-slot buffers of max_bytes bytes and max_msgs entries for the
+ *   four-slot ring; (0, 0) disables and frees them (the default: no kernel is enqueued).  Waits
+ *   for the chains in flight; TXV_ESTATE while a submitted batch has not been waited for.  While
+ *   the sink is on, batches are staged without the host validator lookup (the messages need the
+ *   address bytes in HBM).
+ * txv_gossip_msgs: the entries of the batch `ticket` names, readable from the return of
+ *   txv_wait_votes(ticket) until the slot's next batch is submitted (four submits later; a submit
+ *   into the slot while a read-out is copying fails with TXV_ESTATE, and so does a second read-out
+ *   of the slot meanwhile).  out = the buffer as built: message k at off_out[k], a multiple of 16,
+ *   len_out[k] bytes long, zero padding up to the next message; idx_out[k] = the vote's index in
+ *   the batch (the caller keeps its own sender ids and skips the peer that sent vote idx);
+ *   flag_out[k] as above.  Any output may be NULL; *n_out = entries, *bytes_out = buffer bytes.
+ *   Only the bytes and descriptors used are copied, on a stream of the read-out's own and without
+ *   the context's lock, so batches in flight are not stalled.
+ *   TXV_ESTATE when the sink is off, the ticket has not been waited for, its slot was reused, or
+ *   the batch was staged with txv_stage before the sink was enabled and took the host validator
+ *   lookup (no messages are built for it: stage it again with the sink on);
+ *   TXV_ECAPACITY when the batch overflowed the sink (*n_out, *bytes_out = what it needs; the
+ *   batch's TxFlow results are not affected and the TxFlow is not poisoned) or `cap` / `msg_cap` is
+ *   too small (*n_out, *bytes_out = the counts; nothing written).  No validator-count limit. */
+#define TXV_GOSSIP_OK 0
+#define TXV_GOSSIP_HOST 1
+#define TXV_GOSSIP_UNENCODABLE 2
+int txv_gossip_sink_enable(txv_ctx* ctx, uint64_t max_bytes, uint32_t max_msgs);
+int txv_gossip_msgs(txv_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* off_out,
+                    uint32_t* len_out, uint32_t* idx_out, uint8_t* flag_out, uint32_t msg_cap,
+                    uint32_t* n_out, uint64_t* bytes_out);
 
 /* Tally readers for the TxVoteSet of txhash.  Returns 1 if the set exists, 0 if not. */
 int txv_query_tx(txv_ctx* ctx, const uint8_t* txhash, uint32_t len, int64_t* sum, uint8_t* maj23);
