@@ -300,6 +300,32 @@ struct txv_ctx {
   // signer slots (load generator)
   uint32_t n_signers = 0;
   uint32_t *d_sk_scal = nullptr, *d_sk_araw = nullptr, *d_sk_prefix = nullptr, *d_sk_pub = nullptr;
+  uint32_t* d_sk_addr = nullptr;       // [n_signers][5] SHA-256(pub)[:20], beside the slots' public keys
+  std::vector<uint8_t> sk_pub;         // [n_signers][32] the slots' public keys on the host ("am I a validator")
+  // the sign ring (txv_sign_txs_submit / txv_sign_txs_wait; kernels_sign.hip): ticket t on entry
+  // (t - 1) % TXV_SIGN_RING, each with its own pinned staging and device copies of the txs and
+  // timestamps (grown as ensure_slot grows a slot's), the chain's scratch, the event behind its
+  // uploads (copy stream) and the events around its kernels (key stream).  sign_mu serialises the
+  // submits; the entries are guarded by mu
+  struct SignEntry {
+    uint64_t ticket = 0;               // the chain in flight on this entry (0 = free)
+    bool waiting = false;              // a txv_sign_txs_wait is in its event wait
+    uint32_t n_cap = 0, mw_cap = 0;
+    uint64_t tx_cap = 0;
+    uint8_t *h_tx = nullptr, *d_tx = nullptr;
+    uint64_t *h_off = nullptr, *d_off = nullptr;
+    uint32_t *h_len = nullptr, *d_len = nullptr;
+    int64_t *h_sec = nullptr, *d_sec = nullptr;
+    int32_t *h_nanos = nullptr, *d_nanos = nullptr;
+    uint64_t* d_msg = nullptr;
+    uint32_t *d_msg_len = nullptr, *d_r = nullptr, *d_rpts = nullptr, *d_renc = nullptr;
+    hipEvent_t up_ev = nullptr, ev0 = nullptr, ev = nullptr;
+    txv_route_meta meta{};
+  } sign[TXV_SIGN_RING];
+  std::mutex sign_mu;
+  uint64_t sign_next = 1;              // next sign ticket; guarded by mu
+  uint64_t sk_gen = 0;                 // txv_keygen calls so far (a sign submit notices new slots)
+  float sign_ms = 0.f;                 // device time of the last waited chain (txv_sign_txs_ms)
   Slot slots[kSlots];
   // the route ring (txv_route_submit_* / txv_route_wait; kernels_route.hip): ticket t on entry
   // (t - 1) % kRouteRing with slot kRouteSlot + entry for its columns and its own scratch -- per-vote
@@ -1602,6 +1628,8 @@ void txv_destroy(txv_ctx* c) {
   (void)hipSetDevice(c->device);
   for (auto& e : c->route)   // routes still in flight write the caller's buffers and the entries' scratch
     if (e.ticket && e.ev) (void)hipEventSynchronize(e.ev);
+  for (auto& e : c->sign)    // signs still in flight read the entries' staging and write the caller's buffer
+    if (e.ticket && e.ev) (void)hipEventSynchronize(e.ev);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
@@ -1639,7 +1667,13 @@ void txv_destroy(txv_ctx* c) {
     if (e.ev) (void)hipEventDestroy(e.ev);
   }
   for (const auto& rg : c->registered) (void)hipHostUnregister((void*)rg.first);
-  dfree(c->d_sk_scal); dfree(c->d_sk_araw); dfree(c->d_sk_prefix); dfree(c->d_sk_pub);
+  dfree(c->d_sk_scal); dfree(c->d_sk_araw); dfree(c->d_sk_prefix); dfree(c->d_sk_pub); dfree(c->d_sk_addr);
+  for (auto& e : c->sign) {
+    hfree(e.h_tx); dfree(e.d_tx); hfree(e.h_off); dfree(e.d_off); hfree(e.h_len); dfree(e.d_len);
+    hfree(e.h_sec); dfree(e.d_sec); hfree(e.h_nanos); dfree(e.d_nanos);
+    dfree(e.d_msg); dfree(e.d_msg_len); dfree(e.d_r); dfree(e.d_rpts); dfree(e.d_renc);
+    for (hipEvent_t ev : {e.up_ev, e.ev0, e.ev}) if (ev) (void)hipEventDestroy(ev);
+  }
   dfree(c->d_chain); dfree(c->d_chain_sign);
   dfree(c->d_pk_sig); dfree(c->d_pk_len); dfree(c->d_pk_keys); hfree(c->h_pk_sig); hfree(c->h_pk_len); hfree(c->h_pk_keys);
   dfree(c->d_wd_wire); hfree(c->h_wd_wire); dfree(c->d_wd_off); hfree(c->h_wd_off); dfree(c->d_wd_len); hfree(c->h_wd_len);
@@ -1833,6 +1867,8 @@ int txv_set_validators(txv_ctx* c, const uint8_t* pubs32, const int64_t* powers,
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n > c->cfg.max_validators) { c->err = "validator set exceeds max_validators"; return TXV_ECAPACITY; }
+  for (auto& e : c->sign)   // a sign in flight reads the chain id and the base-point table this call may replace
+    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
   c->n_vals = n;
   c->pubs.assign(pubs32, pubs32 + (size_t)n * 32);
   c->powers.assign(powers, powers + n);
@@ -2247,17 +2283,25 @@ int txv_keygen(txv_ctx* c, const uint8_t* seeds32, uint32_t n, uint8_t* pubs_out
   if (!c || (!seeds32 && n)) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
+  for (auto& e : c->sign)   // a sign in flight reads the old slots
+    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
   uint32_t* d_seeds = nullptr;
   int r;
   if ((r = dalloc(c, &d_seeds, (size_t)n * 8)) || (r = dalloc(c, &c->d_sk_scal, (size_t)n * 8)) ||
       (r = dalloc(c, &c->d_sk_araw, (size_t)n * 8)) || (r = dalloc(c, &c->d_sk_prefix, (size_t)n * 8)) ||
-      (r = dalloc(c, &c->d_sk_pub, (size_t)n * 8)))
+      (r = dalloc(c, &c->d_sk_pub, (size_t)n * 8)) || (r = dalloc(c, &c->d_sk_addr, (size_t)n * 5)))
     return r;
+  c->n_signers = 0;
+  ++c->sk_gen;
+  c->sk_pub.assign((size_t)n * 32, 0);
   if (n) {
     HIP_TRY(c, hipMemcpyAsync(d_seeds, seeds32, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, txv_launch_keygen(d_seeds, n, c->d_btable4,c->d_sk_scal, c->d_sk_araw, c->d_sk_prefix, c->d_sk_pub,
                                  c->stream));
     if (pubs_out) HIP_TRY(c, hipMemcpyAsync(pubs_out, c->d_sk_pub, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    // for txv_sign_txs: each slot's address beside its key, and the keys on the host
+    HIP_TRY(c, txv_launch_sign_addr(c->d_sk_pub, n, c->d_sk_addr, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->sk_pub.data(), c->d_sk_pub, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   dfree(d_seeds);
@@ -2933,6 +2977,13 @@ int route_drain(txv_ctx* c) {
   return TXV_OK;
 }
 
+// the same for the sign ring (txv_sign_txs_submit)
+int sign_drain(txv_ctx* c) {
+  for (auto& e : c->sign)
+    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
+  return TXV_OK;
+}
+
 // A synchronous route (submit + wait in one call) that leaves the ring idle takes its entry again
 // next time: the next ticket is t + kRouteRing, on entry (t - 1) % kRouteRing like t.  A caller
 // that never pipelines then keeps to one entry's slot and scratch (one allocation, warm buffers),
@@ -3371,6 +3422,7 @@ int txv_reset_flow(txv_ctx* c) {
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (int r = route_drain(c)) return r;
+  if (int r = sign_drain(c)) return r;
   if (!c->n_vals) return TXV_OK;
   return reset_tally(c, false);
 }
@@ -3383,6 +3435,7 @@ int txv_sync(txv_ctx* c) {
     std::lock_guard<std::mutex> g(c->mu);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = route_drain(c)) return r;
+    if (int r = sign_drain(c)) return r;
   }
   HIP_TRY(c, hipStreamSynchronize(c->vstream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3463,6 +3516,271 @@ int txv_fe_selftest(txv_ctx* c, const uint32_t* a, const uint32_t* b, uint32_t* 
   HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   dfree(da); dfree(db); dfree(dout);
+  return TXV_OK;
+}
+
+}  // extern "C"
+
+// ---- Reactor.signTxRoutine's body for a batch of txs (txvotepool/reactor.go:108-126; kernels_sign.hip) ----
+namespace {
+
+// "only sign if I'm a validator" (reactor.go:111): the slot's public key is in the registry
+bool signer_is_validator(const txv_ctx* c, uint32_t signer) {
+  const uint8_t* pub = c->sk_pub.data() + (size_t)signer * 32;
+  uint8_t h[32];
+  txv_sha256_bytes(pub, 32, h);
+  const auto it = c->addr_index.find(std::string((const char*)h, 20));
+  return it != c->addr_index.end() && !memcmp(c->pubs.data() + (size_t)it->second * 32, pub, 32);
+}
+
+// the entry's staging and scratch for n votes, tx_bytes of txs and mw SignBytes words per vote
+int ensure_sign_entry(txv_ctx* c, txv_ctx::SignEntry& e, uint32_t n, uint64_t tx_bytes, uint32_t mw) {
+  int r;
+  if (!e.ev) {
+    HIP_TRY(c, hipEventCreateWithFlags(&e.up_ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreate(&e.ev0));
+    HIP_TRY(c, hipEventCreate(&e.ev));
+  }
+  const uint32_t need = std::max<uint32_t>(n, 64);
+  if (e.n_cap < need || e.mw_cap < mw) {
+    const uint32_t cap = std::max(need, e.n_cap), w = std::max(mw, e.mw_cap);
+    const size_t np = ((size_t)cap + 63) / 64 * 64;
+    e.n_cap = 0;
+    if ((r = halloc(c, &e.h_off, np)) || (r = dalloc(c, &e.d_off, np)) || (r = halloc(c, &e.h_len, np)) ||
+        (r = dalloc(c, &e.d_len, np)) || (r = halloc(c, &e.h_sec, np)) || (r = dalloc(c, &e.d_sec, np)) ||
+        (r = halloc(c, &e.h_nanos, np)) || (r = dalloc(c, &e.d_nanos, np)) || (r = dalloc(c, &e.d_msg, (size_t)w * np)) ||
+        (r = dalloc(c, &e.d_msg_len, np)) || (r = dalloc(c, &e.d_r, 8 * np)) ||
+        (r = dalloc(c, &e.d_rpts, (size_t)TXV_RPTS_WORDS * np)) || (r = dalloc(c, &e.d_renc, 8 * np)))
+      return r;
+    e.n_cap = (uint32_t)np;
+    e.mw_cap = w;
+  }
+  if (e.tx_cap < tx_bytes + 16) {   // 16 bytes behind the txs: the hash reads whole aligned words
+    const uint64_t cap = std::max<uint64_t>(tx_bytes + 16, e.tx_cap * 2);
+    e.tx_cap = 0;
+    if ((r = halloc(c, &e.h_tx, cap)) || (r = dalloc(c, &e.d_tx, cap))) return r;
+    e.tx_cap = cap;
+  }
+  return TXV_OK;
+}
+
+int sign_submit(txv_ctx* c, const txv_txs* t, uint32_t signer, int64_t height, void* dst, uint64_t cap, uint64_t* ticket) {
+  // sign_mu: one submit at a time, so the next ticket's entry is this call's from the checks to
+  // the launch.  The context's lock is held for the checks and for the enqueue only, not while
+  // the txs are copied into the entry's staging (256 MiB for 1M txs of 256 bytes)
+  std::lock_guard<std::mutex> sg(c->sign_mu);
+  const uint32_t n = t->n;
+  uint32_t m = 0, mw = 0, chain_len = 0;
+  uint64_t tx_bytes = 0, tk = 0, set_gen = 0, sk_gen = 0;
+  txv_ctx::SignEntry* ep = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->n_vals) { c->err = "no validator set"; return TXV_ESTATE; }
+    if (signer >= c->n_signers) { c->err = "signer is not a txv_keygen slot"; return TXV_EINVAL; }
+    if (n > c->cfg.max_batch) { c->err = "batch exceeds max_batch"; return TXV_EINVAL; }
+    // the buffer's TxHash offsets (64 i) are 32-bit
+    if (n >= (1u << 26)) { c->err = "txv_sign_txs: at most 2^26 - 1 txs per call"; return TXV_EINVAL; }
+    if (cap < txv_sign_txs_bytes(n)) { c->err = "cap below txv_sign_txs_bytes(n) = " + std::to_string(txv_sign_txs_bytes(n)); return TXV_EINVAL; }
+    if (!txv_base_walk_supported(c->b_w)) { c->err = "no base-point walk for window " + std::to_string(c->b_w); return TXV_ESTATE; }
+    chain_len = (uint32_t)c->chain.size();
+    for (uint32_t i = 0; i < n; ++i) {
+      // amino's time range, by the rule the SignBytes encoders apply; the reference's time.Now() never leaves it
+      if (txv_host::sign_bytes_len(height, 64, t->ts_sec[i], t->ts_nanos[i], chain_len) < 0) {
+        c->err = "tx " + std::to_string(i) + ": timestamp outside amino's time range";
+        return TXV_EINVAL;
+      }
+      tx_bytes += t->tx_len[i];
+      if (t->tx_len[i] && !t->tx) { c->err = "tx bytes missing"; return TXV_EINVAL; }
+    }
+    tk = c->sign_next;
+    ep = &c->sign[(tk - 1) % TXV_SIGN_RING];
+    if (ep->ticket) { c->err = "two signs already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+    // not a validator: a buffer of zero votes
+    m = signer_is_validator(c, signer) ? n : 0u;
+    mw = (signbytes_bound(64, chain_len) + 7) / 8;
+    if (int r = ensure_sign_entry(c, *ep, m, m ? tx_bytes : 0, mw)) return r;
+    set_gen = c->set_gen;
+    sk_gen = c->sk_gen;
+  }
+  txv_ctx::SignEntry& e = *ep;
+  const uint32_t np = (m + 63) / 64 * 64;
+  if (m) {   // the free entry's staging is this call's alone (sign_mu)
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+      e.h_off[i] = o;
+      e.h_len[i] = t->tx_len[i];
+      e.h_sec[i] = t->ts_sec[i];
+      e.h_nanos[i] = t->ts_nanos[i];
+      o += t->tx_len[i];
+    }
+    c->pool->parallel_for(m, [&](uint32_t lo, uint32_t hi) {
+      for (uint32_t i = lo; i < hi; ++i)
+        if (e.h_len[i]) memcpy(e.h_tx + e.h_off[i], t->tx + t->tx_off[i], e.h_len[i]);
+    }, 4096);
+    memset(e.h_tx + tx_bytes, 0, 16);
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  // txv_set_validators / txv_keygen on another thread meanwhile: the chain id, the registry or the
+  // slot this call checked are gone.  Nothing was enqueued or written
+  if (c->set_gen != set_gen || c->sk_gen != sk_gen) {
+    c->err = "the validator set or the signer slots changed during the submit";
+    return TXV_ESTATE;
+  }
+  hipStream_t up = c->copy_stream, ks = c->key_stream;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(e.d_tx, e.h_tx, tx_bytes + 16, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(e.d_off, e.h_off, (size_t)m * 8, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(e.d_len, e.h_len, (size_t)m * 4, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(e.d_sec, e.h_sec, (size_t)m * 8, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(e.d_nanos, e.h_nanos, (size_t)m * 4, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipEventRecord(e.up_ev, up));
+    HIP_TRY(c, hipStreamWaitEvent(ks, e.up_ev, 0));
+  }
+  SignTxArgs a{};
+  a.n = m; a.n_pad = np; a.msg_words = mw; a.chain_len = chain_len; a.height = height;
+  a.tx = e.d_tx; a.tx_off = e.d_off; a.tx_len = e.d_len; a.ts_sec = e.d_sec; a.ts_nanos = e.d_nanos;
+  a.prefix = c->d_sk_prefix + (size_t)signer * 8; a.araw = c->d_sk_araw + (size_t)signer * 8;
+  a.pub = c->d_sk_pub + (size_t)signer * 8; a.addr = c->d_sk_addr + (size_t)signer * 5;
+  a.dst = static_cast<uint8_t*>(dst);
+  a.bytes = txv_route::layout(m, 64ull * m, TXV_ROUTE_TXKEY, a.off);
+  a.msg = e.d_msg; a.msg_len = e.d_msg_len; a.rbuf = e.d_r; a.rpts = e.d_rpts; a.renc = e.d_renc;
+  SignBytesArgs sb{};
+  sb.n = m; sb.n_pad = np; sb.msg_words = mw; sb.chain_len = chain_len;
+  sb.height = reinterpret_cast<const int64_t*>(a.dst + a.off[txv_route::kHeight]);
+  sb.ts_sec = reinterpret_cast<const int64_t*>(a.dst + a.off[txv_route::kSec]);
+  sb.ts_nanos = reinterpret_cast<const int32_t*>(a.dst + a.off[txv_route::kNanos]);
+  sb.txhash_off = reinterpret_cast<const uint32_t*>(a.dst + a.off[txv_route::kOff]);
+  sb.txhash_len = reinterpret_cast<const uint32_t*>(a.dst + a.off[txv_route::kLen]);
+  sb.txhash = a.dst + a.off[txv_route::kArena];
+  sb.chain = c->d_chain; sb.msg_len = e.d_msg_len; sb.nil = nullptr; sb.msg = e.d_msg;
+  // the chain reads no TxFlow state: on the key stream, behind the uploads
+  HIP_TRY(c, hipEventRecord(e.ev0, ks));
+  HIP_TRY(c, txv_launch_sign_build(&a, ks));
+  HIP_TRY(c, txv_launch_signbytes(&sb, ks));
+  HIP_TRY(c, txv_launch_sign_nonce(&a, ks));
+  HIP_TRY(c, txv_launch_base_walk(c->b_w, c->d_btable, e.d_r, m, np, e.d_rpts, (uint32_t)c->n_cus, ks));
+  HIP_TRY(c, txv_launch_base_encode(e.d_rpts, m, np, e.d_renc, ks));
+  HIP_TRY(c, txv_launch_sign_finish(&a, ks));
+  HIP_TRY(c, hipEventRecord(e.ev, ks));
+  e.meta = txv_route_meta{m, m ? 64u : 0u, TXV_ROUTE_TXKEY, 0u, 64ull * m, a.bytes};
+  e.ticket = tk;
+  e.waiting = false;
+  c->sign_next = tk + 1;
+  *ticket = tk;
+  return TXV_OK;
+}
+
+int sign_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta) {
+  txv_ctx::SignEntry& e = c->sign[(ticket - 1) % TXV_SIGN_RING];
+  hipEvent_t done;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (e.ticket != ticket || e.waiting) { c->err = "txv_sign_txs_wait: no such sign ticket in flight"; return TXV_ESTATE; }
+    e.waiting = true;
+    done = e.ev;
+  }
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipEventSynchronize(done);
+  std::lock_guard<std::mutex> g(c->mu);
+  e.ticket = 0;
+  e.waiting = false;
+  if (he != hipSuccess) {
+    c->err = std::string("txv_sign_txs_wait: ") + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
+  (void)hipEventElapsedTime(&c->sign_ms, e.ev0, e.ev);
+  *meta = e.meta;
+  return TXV_OK;
+}
+
+// A synchronous sign (submit + wait in one call) that leaves the ring idle takes its entry again
+// next time, as route_sync_done does for the route ring: a caller that never pipelines keeps to one
+// entry's staging and scratch.  Skipped while a submit is under way (it has read sign_next).
+void sign_sync_done(txv_ctx* c, uint64_t t) {
+  std::unique_lock<std::mutex> sl(c->sign_mu, std::try_to_lock);
+  if (!sl.owns_lock()) return;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->sign_next != t + 1) return;
+  for (const auto& e : c->sign)
+    if (e.ticket) return;
+  c->sign_next = t + TXV_SIGN_RING;
+}
+
+bool sign_args_ok(const txv_txs* t, const void* dst) {
+  if (!t || !dst || (uintptr_t)dst % 16) return false;
+  return !t->n || (t->tx_off && t->tx_len && t->ts_sec && t->ts_nanos);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t txv_sign_txs_bytes(uint32_t n) { return txv_route_bytes(n, 64ull * n, TXV_ROUTE_TXKEY); }
+
+int txv_sign_txs_submit(txv_ctx* c, const txv_txs* txs, uint32_t signer, int64_t height, void* dst_dev, uint64_t cap,
+                        uint64_t* sign_ticket) {
+  if (!c || !sign_ticket || !sign_args_ok(txs, dst_dev)) return TXV_EINVAL;
+  return sign_submit(c, txs, signer, height, dst_dev, cap, sign_ticket);
+}
+
+int txv_sign_txs_wait(txv_ctx* c, uint64_t sign_ticket, txv_route_meta* meta_out) {
+  if (!c || !sign_ticket || !meta_out) return TXV_EINVAL;
+  return sign_wait(c, sign_ticket, meta_out);
+}
+
+int txv_sign_txs(txv_ctx* c, const txv_txs* txs, uint32_t signer, int64_t height, void* dst_dev, uint64_t cap,
+                 txv_route_meta* meta_out) {
+  if (!c || !meta_out || !sign_args_ok(txs, dst_dev)) return TXV_EINVAL;
+  uint64_t t = 0;
+  if (int r = sign_submit(c, txs, signer, height, dst_dev, cap, &t)) return r;
+  const int r = sign_wait(c, t, meta_out);
+  sign_sync_done(c, t);
+  return r;
+}
+
+int txv_sign_txs_ms(txv_ctx* c, float* ms) {
+  if (!c || !ms) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  *ms = c->sign_ms;
+  return TXV_OK;
+}
+
+int txv_scalarmult_base(txv_ctx* c, const uint8_t* scalars32, uint32_t n, uint8_t* enc_out) {
+  if (!c || ((!scalars32 || !enc_out) && n)) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->n_vals || !c->d_btable) { c->err = "no validator set"; return TXV_ESTATE; }
+  if (!txv_base_walk_supported(c->b_w)) { c->err = "no base-point walk for window " + std::to_string(c->b_w); return TXV_ESTATE; }
+  if (n > c->cfg.max_batch) { c->err = "batch exceeds max_batch"; return TXV_EINVAL; }
+  for (uint32_t i = 0; i < n; ++i)
+    if (scalars32[(size_t)i * 32 + 31] & 0xE0) { c->err = "scalar " + std::to_string(i) + " is not below 2^253"; return TXV_EINVAL; }
+  if (!n) return TXV_OK;
+  const size_t np = ((size_t)n + 63) / 64 * 64;
+  std::vector<uint32_t> h(8 * np, 0);
+  for (uint32_t i = 0; i < n; ++i)
+    for (int j = 0; j < 8; ++j) h[(size_t)j * np + i] = le32(scalars32 + (size_t)i * 32 + 4 * j);
+  uint32_t *d_s = nullptr, *d_p = nullptr, *d_e = nullptr;
+  int r;
+  if ((r = dalloc(c, &d_s, 8 * np)) || (r = dalloc(c, &d_p, (size_t)TXV_RPTS_WORDS * np)) || (r = dalloc(c, &d_e, 8 * np))) {
+    dfree(d_s); dfree(d_p); dfree(d_e);
+    return r;
+  }
+  hipStream_t ks = c->key_stream;
+  hipError_t he = hipMemcpyAsync(d_s, h.data(), 8 * np * 4, hipMemcpyHostToDevice, ks);
+  if (he == hipSuccess) he = txv_launch_base_walk(c->b_w, c->d_btable, d_s, n, (uint32_t)np, d_p, (uint32_t)c->n_cus, ks);
+  if (he == hipSuccess) he = txv_launch_base_encode(d_p, n, (uint32_t)np, d_e, ks);
+  if (he == hipSuccess) he = hipMemcpyAsync(h.data(), d_e, 8 * np * 4, hipMemcpyDeviceToHost, ks);
+  if (he == hipSuccess) he = hipStreamSynchronize(ks);
+  dfree(d_s); dfree(d_p); dfree(d_e);
+  if (he != hipSuccess) { c->err = std::string("txv_scalarmult_base: ") + hipGetErrorString(he); return TXV_EDEVICE; }
+  for (uint32_t i = 0; i < n; ++i)
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t w = h[(size_t)j * np + i];
+      uint8_t* o = enc_out + (size_t)i * 32 + 4 * j;
+      o[0] = (uint8_t)w; o[1] = (uint8_t)(w >> 8); o[2] = (uint8_t)(w >> 16); o[3] = (uint8_t)(w >> 24);
+    }
   return TXV_OK;
 }
 

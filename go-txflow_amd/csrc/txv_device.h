@@ -77,6 +77,31 @@ struct SignArgs {
   uint32_t* sig;               // [16][n_pad] output
 };
 
+// Reactor.signTxRoutine's body for a batch of txs (kernels_sign.hip; include/txvote.h
+// txv_sign_txs_submit): one signer's TxVotes built and signed straight into a route buffer
+// (route.h, TXV_ROUTE_TXKEY, no nil column; off = txv_route::layout(n, 64 n, TXV_ROUTE_TXKEY))
+struct SignTxArgs {
+  uint32_t n, n_pad, msg_words, chain_len;
+  int64_t height;              // state.LastBlockHeight
+  const uint8_t* tx;           // tx bytes (staged arena, 16 bytes of padding behind it)
+  const uint64_t* tx_off;      // [n] into tx
+  const uint32_t* tx_len;      // [n]
+  const int64_t* ts_sec;       // [n]
+  const int32_t* ts_nanos;     // [n]
+  const uint32_t* prefix;      // [8] the signer slot's nonce prefix
+  const uint32_t* araw;        // [8] its clamped secret scalar
+  const uint32_t* pub;         // [8] its public key
+  const uint32_t* addr;        // [5] its address, SHA-256(pub)[:20]
+  uint8_t* dst;                // the route buffer (16-byte aligned)
+  uint64_t off[12];            // its column offsets (txv_route::Col)
+  uint64_t bytes;              // its size
+  uint64_t* msg;               // [msg_words][n_pad] SignBytes (txv_k_signbytes' layout)
+  uint32_t* msg_len;           // [n_pad]
+  uint32_t* rbuf;              // [8][n_pad] the nonces r
+  uint32_t* rpts;              // [TXV_RPTS_WORDS][n_pad] R' = [r]B as (X, Y, Z) + the encode pass's prefix products
+  uint32_t* renc;              // [8][n_pad] the canonical encodings R
+};
+
 // TxVoteMessage wire decode (kernels_wire.hip): statuses are include/txvote.h's TXV_WIRE_*
 // (0 ok, 1 too large, 2 amino error, 3 empty/nil).  Output: one 160-byte record per message
 // (TXV_WIRE_REC_WORDS u32, written as one contiguous stream), word layout:
@@ -129,6 +154,18 @@ hipError_t txv_launch_scalarmult(int wb, int wa, const VerifyArgs* args, uint32_
 hipError_t txv_launch_keygen(const uint32_t* seeds_le, uint32_t n, const uint32_t* btable, uint32_t* scal,
                              uint32_t* araw, uint32_t* prefix, uint32_t* pub, hipStream_t st);
 hipError_t txv_launch_sign(const SignArgs* args, hipStream_t st);
+// the batch signer (kernels_sign.hip).  sign_addr: addr[s] = SHA-256(pub[s])[:20] per signer slot.
+// sign_build: votes + frame of the route buffer, msg_len; sign_nonce: r; base_walk: R' = [r]B over
+// the base-point table of window wb (scalars [8][n_pad], any value below 2^253) into rpts;
+// base_encode: rpts -> canonical encodings [8][n_pad]; sign_finish: k, S, the signature column
+hipError_t txv_launch_sign_addr(const uint32_t* pubs_le, uint32_t n, uint32_t* addr_words, hipStream_t st);
+hipError_t txv_launch_sign_build(const SignTxArgs* args, hipStream_t st);
+hipError_t txv_launch_sign_nonce(const SignTxArgs* args, hipStream_t st);
+bool txv_base_walk_supported(int wb);
+hipError_t txv_launch_base_walk(int wb, const uint32_t* btable, const uint32_t* scal, uint32_t n, uint32_t n_pad,
+                                uint32_t* rpts, uint32_t n_cus, hipStream_t st);
+hipError_t txv_launch_base_encode(uint32_t* rpts, uint32_t n, uint32_t n_pad, uint32_t* enc, hipStream_t st);
+hipError_t txv_launch_sign_finish(const SignTxArgs* args, hipStream_t st);
 hipError_t txv_launch_valu_probe(int op, uint32_t* out, uint32_t blocks, int iters, hipStream_t st);
 hipError_t txv_launch_signbytes(const SignBytesArgs* args, hipStream_t st);
 bool txv_k1b_fusable(int wb, const VerifyArgs* args);   // the launch takes the work-stealing K1b

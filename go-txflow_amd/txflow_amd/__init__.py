@@ -119,6 +119,12 @@ class _Votes(ctypes.Structure):
                 ("txkey", ctypes.c_void_p)]
 
 
+class _Txs(ctypes.Structure):
+    """txv_txs (include/txvote.h): a batch of mempool txs for Context.sign_txs"""
+    _fields_ = [("n", ctypes.c_uint32), ("tx", ctypes.c_void_p), ("tx_off", ctypes.c_void_p),
+                ("tx_len", ctypes.c_void_p), ("ts_sec", ctypes.c_void_p), ("ts_nanos", ctypes.c_void_p)]
+
+
 class _PoolCfg(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("cache_size", ctypes.c_uint32), ("max_txs_bytes", ctypes.c_uint64),
                 ("max_msg_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -139,6 +145,7 @@ ROUTE_META_DTYPE = np.dtype([("n", "<u4"), ("max_txhash_len", "<u4"), ("flags", 
                              ("arena_bytes", "<u8"), ("bytes", "<u8")])
 ROUTE_TXKEY, ROUTE_NIL = 0x1, 0x2
 ROUTE_RING = 4   # TXV_ROUTE_RING: route tickets in flight per context
+SIGN_RING = 2    # TXV_SIGN_RING: sign tickets in flight per context
 
 
 _lib = None
@@ -264,6 +271,13 @@ def lib():
             "txv_gossip_sink_enable": ([vp, ctypes.c_uint64, u32], ctypes.c_int),
             "txv_gossip_msgs": ([vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, vp, u32, ctypes.POINTER(u32),
                                  ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_sign_txs_bytes": ([u32], ctypes.c_uint64),
+            "txv_sign_txs_submit": ([vp, ctypes.POINTER(_Txs), u32, i64, vp, ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_sign_txs_wait": ([vp, ctypes.c_uint64, vp], ctypes.c_int),
+            "txv_sign_txs": ([vp, ctypes.POINTER(_Txs), u32, i64, vp, ctypes.c_uint64, vp], ctypes.c_int),
+            "txv_sign_txs_ms": ([vp, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "txv_scalarmult_base": ([vp, vp, u32, vp], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -295,7 +309,9 @@ EXPORTED_SYMBOLS = [
     "txv_ingest_admit_submit", "txv_ingest_admit_finish",
     "txv_update_sink_enable", "txv_update_list", "txv_pool_update_fired",
     "txv_store_sink_enable", "txv_store_records",
-    "txv_gossip_sink_enable", "txv_gossip_msgs"]
+    "txv_gossip_sink_enable", "txv_gossip_msgs",
+    "txv_sign_txs_bytes", "txv_sign_txs_submit", "txv_sign_txs_wait", "txv_sign_txs", "txv_sign_txs_ms",
+    "txv_scalarmult_base"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -403,6 +419,47 @@ class VoteBatch:
     def txhash(self, i: int) -> bytes:
         o, l = int(self.txhash_off[i]), int(self.txhash_len[i])
         return self.txhash_arena[o:o + l].tobytes()
+
+
+class TxBatch:
+    """A batch of mempool txs matching txv_txs (include/txvote.h): raw tx bytes in one arena and the
+    Timestamp NewTxVote stamps on each tx's vote (the caller's time.Now())."""
+
+    def __init__(self, txs: Sequence[bytes] = (), ts_sec=None, ts_nanos=None, *, arena=None, off=None, length=None):
+        c = np.ascontiguousarray
+        if arena is None:
+            ln = np.array([len(t) for t in txs], np.uint32)
+            arena = np.frombuffer(b"".join(txs), np.uint8)
+            off = np.concatenate([[0], np.cumsum(ln[:-1], dtype=np.uint64)]).astype(np.uint64) if len(txs) else np.zeros(0, np.uint64)
+            length = ln
+        self.arena = c(arena, dtype=np.uint8)
+        if self.arena.size == 0:
+            self.arena = np.zeros(1, np.uint8)
+        self.off = c(off, dtype=np.uint64)
+        self.length = c(length, dtype=np.uint32)
+        self.n = int(self.length.size)
+        self.ts_sec = c(np.zeros(self.n, np.int64) if ts_sec is None else ts_sec, dtype=np.int64)
+        self.ts_nanos = c(np.zeros(self.n, np.int32) if ts_nanos is None else ts_nanos, dtype=np.int32)
+        assert self.off.size == self.n and self.ts_sec.size == self.n and self.ts_nanos.size == self.n
+
+    def tx(self, i: int) -> bytes:
+        o, l = int(self.off[i]), int(self.length[i])
+        return self.arena[o:o + l].tobytes()
+
+    def c_struct(self) -> _Txs:
+        t = _Txs()
+        t.n = self.n
+        t.tx = self.arena.ctypes.data
+        t.tx_off = self.off.ctypes.data
+        t.tx_len = self.length.ctypes.data
+        t.ts_sec = self.ts_sec.ctypes.data
+        t.ts_nanos = self.ts_nanos.ctypes.data
+        return t
+
+
+def sign_txs_bytes(n: int) -> int:
+    """txv_sign_txs_bytes: the size of the route buffer Context.sign_txs writes for n txs"""
+    return int(lib().txv_sign_txs_bytes(n))
 
 
 def route_flags(batch: VoteBatch) -> int:
@@ -962,6 +1019,49 @@ class Context:
         self._chk(lib().txv_sign_votes(self._h, ctypes.byref(vs), signer.ctypes.data, cid, len(cid), out.ctypes.data),
                   "txv_sign_votes")
         return out[:batch.n]
+
+    def sign_txs_submit(self, txs: TxBatch, signer: int, height: int, dst_ptr: int, cap: int) -> int:
+        """txv_sign_txs_submit: Reactor.signTxRoutine's body for a batch of txs -- signer slot
+        `signer`'s own TxVotes (TxKey = SHA-256(tx), TxHash = its hex, the batch's timestamps,
+        Height = height) built and signed on the GPU into one route buffer at device address
+        dst_ptr (16-byte aligned, cap >= sign_txs_bytes(txs.n)).  Returns a sign ticket without
+        waiting for the GPU; up to SIGN_RING in flight (TXV_ESTATE beyond)."""
+        t = ctypes.c_uint64()
+        ts = txs.c_struct()
+        self._chk(lib().txv_sign_txs_submit(self._h, ctypes.byref(ts), signer, height, ctypes.c_void_p(dst_ptr), cap,
+                                            ctypes.byref(t)), "txv_sign_txs_submit")
+        return t.value
+
+    def sign_txs_wait(self, ticket: int):
+        """txv_sign_txs_wait: the buffer's meta (a ROUTE_META_DTYPE scalar: what submit_routed takes)
+        once it is written; n = 0 when the signer is not a validator of the context's set"""
+        meta = np.zeros(1, ROUTE_META_DTYPE)
+        self._chk(lib().txv_sign_txs_wait(self._h, ticket, meta.ctypes.data), "txv_sign_txs_wait")
+        return meta[0]
+
+    def sign_txs(self, txs: TxBatch, signer: int, height: int, dst_ptr: int, cap: int):
+        """txv_sign_txs: sign_txs_submit + sign_txs_wait"""
+        meta = np.zeros(1, ROUTE_META_DTYPE)
+        ts = txs.c_struct()
+        self._chk(lib().txv_sign_txs(self._h, ctypes.byref(ts), signer, height, ctypes.c_void_p(dst_ptr), cap,
+                                     meta.ctypes.data), "txv_sign_txs")
+        return meta[0]
+
+    def sign_txs_ms(self) -> float:
+        """device time (ms) of the last waited sign chain"""
+        ms = ctypes.c_float()
+        self._chk(lib().txv_sign_txs_ms(self._h, ctypes.byref(ms)), "txv_sign_txs_ms")
+        return ms.value
+
+    def scalarmult_base(self, scalars) -> np.ndarray:
+        """txv_scalarmult_base (self-test): the canonical encodings [n, 32] of [s]B for 32-byte
+        little-endian scalars below 2^253, through the signer's walk and encode kernels"""
+        sc = np.ascontiguousarray(np.frombuffer(b"".join(scalars), np.uint8) if not isinstance(scalars, np.ndarray)
+                                  else scalars, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((max(len(sc), 1), 32), np.uint8)
+        self._chk(lib().txv_scalarmult_base(self._h, sc.ctypes.data if len(sc) else None, len(sc), out.ctypes.data),
+                  "txv_scalarmult_base")
+        return out[:len(sc)]
 
     def stage(self, slot: int, batch: VoteBatch):
         vs = batch.c_struct()

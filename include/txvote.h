@@ -41,6 +41,9 @@
  *   txv_route_admitted / txv_submit_routed <- the Receive -> CheckTxWithInfo -> TryAddVote hand-off
  *                         (txvotepool/reactor.go:170-190 -> txvotepool.go:187-261 -> txflow/service.go:
  *                         123-166) across the GPUs of a node, CheckTx on one owner
+ *   txv_sign_txs_submit / txv_sign_txs_wait <- Reactor.signTxRoutine's body for a batch of txs,
+ *                         txvotepool/reactor.go:108-126: NewTxVote types/tx_vote.go:57-71 +
+ *                         privVal.SignTxVote types/priv_validator.go:83-95, into a route buffer
  */
 #ifndef TXVOTE_H
 #define TXVOTE_H
@@ -512,6 +515,71 @@ int txv_route_pack_host(const txv_votes* votes, const uint8_t* pool_status, uint
                         uint64_t stride, txv_route_meta* meta_out);
 int txv_route_view(const void* buf, uint64_t bytes, txv_votes* out);
 int txv_submit_routed(txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta, uint64_t* ticket);
+
+/* ---- sign by batch on the device: a validator's own TxVotes built in HBM ----
+ * <- Reactor.signTxRoutine's body (txvotepool/reactor.go:108-126) for a batch of mempool txs:
+ * NewTxVote(LastBlockHeight, TxHash(tx), TxKey(tx), addr) (types/tx_vote.go:38-45,57-71), then
+ * privVal.SignTxVote(chainID, &vote) (types/priv_validator.go:83-95).  The votes are built and
+ * signed on the GPU and written as ONE route buffer (the layout of txv_route_admitted, flags
+ * TXV_ROUTE_TXKEY, no nil column) at dst_dev: what txv_submit_routed runs TxFlow from, txv_route_view
+ * reads on the host after a copy, and the multi-GPU path ships as it is.
+ *
+ * signer: a txv_keygen slot.  Chain id: the one txv_set_validators gave the context.  height:
+ * state.LastBlockHeight.  Vote i (tx order) carries Height = height, TxKey = SHA-256(tx_i), TxHash =
+ * the 64 upper-case hex characters of that digest (at offset 64 i of the buffer's arena), the
+ * caller's timestamp (the time.Now() NewTxVote stamps), ValidatorAddress = SHA-256(pub)[:20] of the
+ * signer, Signature = RFC 8032 Ed25519 over SignBytes(chainID): the bytes x/crypto's deterministic
+ * ed25519.Sign and txv_sign_votes produce.  *meta_out = the buffer's meta (n, max_txhash_len 64,
+ * flags, arena_bytes 64 n, bytes).  Every byte of [dst_dev, dst_dev + meta.bytes) is written,
+ * whatever the memory held: the buffer is byte-equal to txv_route_pack_host of the same votes.
+ *
+ * "Only sign if I'm a validator" (reactor.go:111): when the signer's public key is not in the
+ * context's registry the call succeeds with a buffer of zero votes (meta.n = 0).
+ *
+ * TXV_ESTATE without a validator set, or when the ring entry holds an unwaited ticket: up to
+ * TXV_SIGN_RING signs in flight, ticket t on entry (t - 1) % TXV_SIGN_RING, waits in any order.
+ * TXV_EINVAL when signer is not a slot, n > max_batch or n >= 2^26 (the buffer's TxHash offsets,
+ * 64 i, are 32-bit), cap < txv_sign_txs_bytes(n), dst_dev is not
+ * 16-byte aligned, or a timestamp is outside amino's time range (ts_nanos outside [0, 1e9), seconds
+ * outside years 1..9999: the rule txv_signbytes applies).  The reference swallows a SignTxVote error
+ * and runs CheckTx on the unsigned vote (reactor.go:120-122), and its time.Now() never leaves that
+ * range; a vote this library cannot encode is refused instead.  A refused call writes nothing.
+ *
+ * The submit enqueues everything and returns without waiting for the GPU.  Host tx bytes and
+ * timestamps may be reused once it returns.  txv_sign_txs is submit + wait on the same code.
+ * txv_sync, txv_reset_flow, txv_keygen, txv_set_validators and txv_destroy wait for the signs in
+ * flight first.  A txv_set_validators or txv_keygen that another thread runs while a submit is
+ * copying its txs makes that submit fail with TXV_ESTATE (nothing enqueued or written).  A
+ * synchronous call that leaves the ring idle takes the same ring entry again next time (its
+ * tickets then advance by TXV_SIGN_RING), so a caller that never pipelines uses one entry's staging.
+ *
+ * Custody: the keys live in the context as txv_keygen left them (expanded secret scalar and nonce
+ * prefix in device memory).  The table lines the walk reads and the variable-time field inversion
+ * depend on the nonce: this is MockPV-grade signing (types/priv_validator.go:83-95), NOT
+ * constant-time, and not a replacement for privval custody of a production key. */
+typedef struct {
+  uint32_t n;
+  const uint8_t*  tx;        /* raw tx bytes, arena */
+  const uint64_t* tx_off;    /* [n] */
+  const uint32_t* tx_len;    /* [n]; 0 is a valid tx */
+  const int64_t*  ts_sec;    /* [n] the Timestamp NewTxVote stamps (time.Now(), tx_vote.go:57-71): the caller's */
+  const int32_t*  ts_nanos;  /* [n] */
+} txv_txs;
+#define TXV_SIGN_RING 2
+/* = txv_route_bytes(n, 64 * n, TXV_ROUTE_TXKEY) */
+uint64_t txv_sign_txs_bytes(uint32_t n);
+int txv_sign_txs_submit(txv_ctx* ctx, const txv_txs* txs, uint32_t signer, int64_t height, void* dst_dev,
+                        uint64_t cap, uint64_t* sign_ticket);
+int txv_sign_txs_wait(txv_ctx* ctx, uint64_t sign_ticket, txv_route_meta* meta_out);
+int txv_sign_txs(txv_ctx* ctx, const txv_txs* txs, uint32_t signer, int64_t height, void* dst_dev, uint64_t cap,
+                 txv_route_meta* meta_out);
+/* measurement: device time (ms) of the last waited sign chain, by events on the stream it ran on */
+int txv_sign_txs_ms(txv_ctx* ctx, float* ms);
+/* measurement / self-test only, like txv_fe_selftest: enc_out[i] = canonical encoding of
+ * [scalars32[i]]B through the signer's walk and encode kernels (scalars little-endian, any 256-bit
+ * value below 2^253; TXV_EINVAL above, TXV_ESTATE without a validator set) */
+int txv_scalarmult_base(txv_ctx* ctx, const uint8_t* scalars32, uint32_t n, uint8_t* enc_out);
+
 /* device pointer + byte size of the per-set committed bitmap (1 bit per tx-set id) */
 int txv_commit_bitmap(txv_ctx* ctx, void** dev_ptr, uint64_t* bytes);
 /* device-to-device copy of the commit bitmap into caller device memory (e.g. an RCCL buffer) */
