@@ -21,6 +21,7 @@
 #include "../../include/txvote.h"
 #include "amino.hpp"
 #include "txv_hash.h"
+#include "routepool_dev.h"
 #include <random>
 
 #include <chrono>
@@ -308,7 +309,7 @@ int pooldev_list_get(txv_ctx* c, PoolDev* s, std::vector<uint8_t>& keys, std::ve
                      std::vector<uint8_t>& ins);
 void pooldev_result(const PoolDev* s, int slot, int64_t res[4]);
 constexpr int kPdRing = 8;   // = PoolDev::kPdRing (runtime.cpp)
-void pooldev_set_occupant(PoolDev* s, int slot, uint64_t id, uint32_t n_upd, uint32_t n);
+void pooldev_set_occupant(PoolDev* s, int slot, uint64_t id, uint32_t n_upd, uint32_t n, bool routed = false);
 bool pooldev_holds(const PoolDev* s, uint64_t id);
 std::mutex& txv_ctx_submit_mu(txv_ctx* c);
 std::mutex& txv_ctx_route_mu(txv_ctx* c);
@@ -322,6 +323,16 @@ void route_checked_sync_done(txv_ctx* c, uint64_t ticket);
 int submit_checked_stage(txv_ctx* c, const txv_votes* v, uint32_t* slot_out);
 int submit_checked_consume(txv_ctx* c, uint32_t slot, PoolDev* dev, uint64_t pool_ticket, const txv_votes* v);
 int submit_checked_run(txv_ctx* c, uint32_t slot, const txv_votes* v, const uint8_t* host_st, int why, uint64_t* ticket);
+// CheckTx and TryAddVote from a route buffer in HBM (runtime.cpp)
+bool routepool_args_ok(const txv_ctx* c, const void* buf, const txv_route_meta* m);
+int routepool_word_get(txv_ctx* c, uint32_t** h, uint32_t** m);
+void routepool_word_put(txv_ctx* c, uint32_t* h, uint32_t* m);
+int routepool_keys(txv_ctx* c, const void* buf, const txv_route_meta* m, uint32_t* guard_m, const uint32_t** d_keys,
+                   const uint32_t** d_sizes, const uint8_t** d_valid, void** after, void** then_stream);
+int routepool_readback(txv_ctx* c, const void* buf, uint64_t bytes, uint8_t* out);
+int submit_routed_checked_stage(txv_ctx* c, const void* buf, const txv_route_meta* m, uint32_t* slot_out);
+int submit_routed_checked_consume(txv_ctx* c, uint32_t slot, PoolDev* dev, uint64_t pool_ticket, uint32_t n);
+int submit_routed_checked_run(txv_ctx* c, uint32_t slot, uint32_t n, const uint8_t* host_st, int why, uint64_t* ticket);
 
 struct txv_pool {
   txv_pool_config cfg{};
@@ -377,6 +388,12 @@ struct txv_pool {
     // Update rides with the next CheckTx batch instead: n_upd entries staged ahead of its votes.)
     bool upd = false;
     uint32_t n_upd = 0;
+    // a batch from a route buffer in HBM (txv_pool_check_routed_submit): the word in mapped host
+    // memory its key kernel sets when the buffer's header is not the caller's meta (held until the
+    // ticket is finished), and whether it did -- every status is TXV_POOL_NOT_CHECKED then and
+    // txv_pool_check_wait returns TXV_EINVAL
+    uint32_t *guard_h = nullptr, *guard_m = nullptr;
+    bool guard_failed = false;
   };
   std::deque<Ticket> tickets;
   // the statuses of the last tickets waited (txv_submit_checked may come after the wait)
@@ -1320,7 +1337,13 @@ int finish_ticket(txv_pool* p, txv_pool::Ticket& t) {
   t.done = true;
   p->infl_len -= (int64_t)t.pushes;
   p->infl_bytes -= (int64_t)t.bytes;
-  if ((t.err = pooldev_finish(t.ctx, p->dev, t.slot, &st, nullptr, nullptr))) return t.err;
+  t.err = pooldev_finish(t.ctx, p->dev, t.slot, &st, nullptr, nullptr);
+  if (t.guard_h) {   // (the key kernel ran before the decisions the finish waited for)
+    t.guard_failed = !t.err && *(volatile uint32_t*)t.guard_h != 0;
+    routepool_word_put(t.ctx, t.guard_h, t.guard_m);
+    t.guard_h = t.guard_m = nullptr;
+  }
+  if (t.err) return t.err;
   if (!t.upd) t.st.assign(st, st + t.n);
   list_counts(p, t.slot);
   return TXV_OK;
@@ -1416,12 +1439,23 @@ int txv_pool_check_dev(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const 
 // has not reported yet), beside the batches in flight.  *done = false: the host path is needed.
 // d_status_copy (or null): the batch's statuses written to HBM there too, and then_stream (or null)
 // made to wait for them -- the ingest's TxFlow chain reads them without a host round trip.
+static int check_dev_submit_locked(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
+                                   const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
+                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done);
 int txv_pool_check_dev_submit(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                               const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
                               uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done) {
+  std::lock_guard<std::mutex> g(p->mu);
+  return check_dev_submit_locked(p, ctx, d_keys, d_sizes, d_valid, valid_ok, n, bytes_bound, after, d_status_copy,
+                                 then_stream, ticket, done);
+}
+
+// (p->mu held; the new ticket is p->tickets.back() when *done)
+static int check_dev_submit_locked(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
+                                   const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
+                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done) {
   *done = false;
   *ticket = 0;
-  std::lock_guard<std::mutex> g(p->mu);
   if (!dev_mode(p) || !n) return TXV_OK;
   if (!dev_caps_ok(p, n, bytes_bound)) return TXV_OK;
   const int64_t max_tx = (int64_t)p->cfg.max_msg_bytes - 8;
@@ -1692,6 +1726,155 @@ int txv_route_checked(txv_ctx* ctx, const txv_votes* v, txv_pool* p, uint64_t po
   return r;
 }
 
+// CheckTx for every vote of a route buffer in ctx's HBM, in buffer order (include/txvote.h) -- what
+// signTxRoutine does with each vote it signed (txvotepool/reactor.go:126).  Device path (the cache
+// in HBM, the engine on ctx's GPU or not bound yet, caps that cannot bind even if all n votes pushed
+// at the largest Size() the meta allows): txv_k_route_keys turns the buffer into the keys / sizes /
+// valid columns the engine decides from and the call is txv_pool_check_dev_submit's from there on;
+// nothing waits for the GPU, nothing crosses the link.  Otherwise the buffer is read back (the one
+// copy that blocks) and its votes go through the host admission.  Either way a vote that is nil or
+// whose signature is above 64 bytes is TXV_POOL_NOT_CHECKED and never touches the pool, and a
+// buffer whose header is not the meta's fails the ticket's wait (Ticket::guard_failed).
+int txv_pool_check_routed_submit(txv_pool* p, txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta,
+                                 uint64_t* ticket) {
+  if (!p || !ticket || !routepool_args_ok(ctx, buf_dev, meta)) return TXV_EINVAL;
+  *ticket = 0;
+  const uint32_t n = meta->n;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (!n) {   // an empty batch (txv_sign_txs of a signer outside the registry): a ticket with no statuses
+    txv_pool::Ticket t;
+    t.id = p->next_ticket;
+    t.ctx = ctx;
+    t.done = true;
+    p->tickets.push_back(std::move(t));
+    *ticket = p->next_ticket++;
+    return TXV_OK;
+  }
+  int r;
+  // the largest Size() a vote of this buffer can have: every varint at its longest
+  const uint64_t size_ub = (uint64_t)txv_host::txvote_size(INT64_MAX, meta->max_txhash_len, -1, 999999999, 20, 64);
+  if (dev_mode(p) && (!p->dev || pooldev_same_device(ctx, p->dev)) && dev_caps_ok(p, n, (uint64_t)n * size_ub)) {
+    uint32_t *gh = nullptr, *gm = nullptr;
+    if ((r = routepool_word_get(ctx, &gh, &gm))) return r;
+    const uint32_t *d_keys, *d_sizes;
+    const uint8_t* d_valid;
+    void *after, *then_stream;
+    bool done = false;
+    if ((r = routepool_keys(ctx, buf_dev, meta, gm, &d_keys, &d_sizes, &d_valid, &after, &then_stream))) {
+      routepool_word_put(ctx, gh, gm);
+      return r;
+    }
+    // (from here on the kernel may still set the word: it is not handed out again unless a ticket
+    // took it and finished)
+    if ((r = check_dev_submit_locked(p, ctx, d_keys, d_sizes, d_valid, 1, n, (uint64_t)n * size_ub, after, nullptr,
+                                     then_stream, ticket, &done)))
+      return r;
+    if (done) {
+      txv_pool::Ticket& t = p->tickets.back();
+      t.guard_h = gh;
+      t.guard_m = gm;
+      pooldev_set_occupant(p->dev, t.slot, t.id, t.n_upd, n, true);   // txv_submit_routed_checked reads its statuses in HBM
+      return TXV_OK;
+    }
+  }
+  // the host path: the buffer read back, its header checked, its votes keyed and sized on the host
+  // workers, the rest is txv_pool_check_submit's host admission
+  std::vector<uint8_t> hb(meta->bytes);
+  if ((r = routepool_readback(ctx, buf_dev, meta->bytes, hb.data()))) return r;
+  txv_pool::Ticket t;
+  t.id = p->next_ticket;
+  t.n = n;
+  t.ctx = ctx;
+  t.done = true;
+  t.st.assign(n, TXV_POOL_NOT_CHECKED);
+  uint64_t h[8];
+  memcpy(h, hb.data(), 64);
+  txv_votes v{};
+  if (!txv_routepool::header_ok(h, n, meta->arena_bytes, meta->flags, meta->max_txhash_len, meta->bytes) ||
+      txv_route_view(hb.data(), hb.size(), &v) != TXV_OK) {
+    t.guard_failed = true;
+  } else {
+    std::vector<uint32_t> ok;
+    ok.reserve(n);
+    for (uint32_t i = 0; i < n; ++i)
+      if (txv_routepool::vote_valid(v.is_nil ? v.is_nil[i] : 0u, v.sig_len[i])) ok.push_back(i);
+    const uint32_t m = (uint32_t)ok.size();
+    p->keys.resize((size_t)m * 32 + 32);
+    p->sizes.resize(m);
+    txv_host_parallel_for(ctx, m, [&](uint32_t lo, uint32_t hi) {
+      for (uint32_t q = lo; q < hi; ++q) {
+        const uint32_t i = ok[q];
+        txv_sha256_bytes(v.sig + (size_t)i * 64, v.sig_len[i], p->keys.data() + (size_t)q * 32);
+        p->sizes[q] = vote_size(&v, i);
+      }
+    });
+    std::vector<uint8_t> st(std::max<uint32_t>(m, 1));
+    if ((r = pool_admit(p, ctx, reinterpret_cast<const Key*>(p->keys.data()), m, st.data()))) return r;
+    for (uint32_t q = 0; q < m; ++q) t.st[ok[q]] = st[q];
+  }
+  p->tickets.push_back(std::move(t));
+  *ticket = p->next_ticket++;
+  return TXV_OK;
+}
+
+int txv_pool_check_routed(txv_pool* p, txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta, uint8_t* status_out) {
+  if (!meta || (meta->n && !status_out)) return TXV_EINVAL;
+  uint64_t t = 0;
+  if (int r = txv_pool_check_routed_submit(p, ctx, buf_dev, meta, &t)) return r;
+  return txv_pool_check_wait(p, t, status_out);
+}
+
+// TryAddVote for the route buffer a CheckTx ticket is deciding (include/txvote.h): txv_submit_routed
+// with the votes the pool did not admit as nil entries.  While the ticket is in the engine's flight
+// slot the nil column is built on the device from the slot's statuses, behind the decisions (no host
+// round trip); otherwise the ticket's statuses are taken on the host, as txv_submit_checked does.
+// Takes the submit lock, then the pool's, then the context's.
+int txv_submit_routed_checked(txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta, txv_pool* p,
+                              uint64_t pool_ticket, uint64_t* ticket) {
+  if (!p || !pool_ticket || !ticket || !routepool_args_ok(ctx, buf_dev, meta)) return TXV_EINVAL;
+  std::lock_guard<std::mutex> so(txv_ctx_submit_mu(ctx));   // no other submit between the steps
+  const uint32_t n = meta->n;
+  uint32_t slot;
+  int r;
+  if ((r = submit_routed_checked_stage(ctx, buf_dev, meta, &slot))) return r;
+  std::vector<uint8_t> st;
+  int why = 0;
+  bool consumed = false;
+  {
+    std::lock_guard<std::mutex> g(p->mu);
+    if (p->dev && pooldev_same_device(ctx, p->dev) && pooldev_holds(p->dev, pool_ticket)) {
+      if ((r = submit_routed_checked_consume(ctx, slot, p->dev, pool_ticket, n)) < 0) return r;
+      consumed = r == 0;
+    }
+    if (!consumed) {
+      auto it = std::find_if(p->tickets.begin(), p->tickets.end(), [&](const txv_pool::Ticket& t) { return t.id == pool_ticket; });
+      if (it == p->tickets.end()) {                  // waited already: its statuses, if still kept
+        why = 1;
+        for (const auto& rc : p->recent)
+          if (rc.first == pool_ticket) {
+            why = rc.second.size() != n ? 2 : 0;
+            if (!why) st = rc.second;
+          }
+      } else if (it->upd) {
+        why = 1;
+      } else if (it->n != n) {
+        why = 2;
+      } else {
+        if (!it->done)
+          for (auto jt = p->tickets.begin(); jt != p->tickets.end(); ++jt) {   // the earlier ones first: append order
+            if (int e = finish_ticket(p, *jt)) return e;
+            if (jt == it) break;
+          }
+        if (it->err) return it->err;
+        st = it->st;
+      }
+    }
+  }
+  if (consumed) return submit_routed_checked_run(ctx, slot, n, nullptr, 0, ticket);
+  if (!why && !n) st.assign(1, 0);   // (a non-null pointer for the empty batch)
+  return submit_routed_checked_run(ctx, slot, n, why ? nullptr : st.data(), why, ticket);
+}
+
 // the statuses of a submitted batch (tickets in submission order); the engine's event is waited
 // for without p->mu held, so batch k+1 can be submitted meanwhile
 int txv_pool_check_wait(txv_pool* p, uint64_t ticket, uint8_t* status_out) {
@@ -1720,10 +1903,14 @@ int txv_pool_check_wait(txv_pool* p, uint64_t ticket, uint8_t* status_out) {
     if (it->id != ticket) continue;
     r = e;
     if (!r && it->n && status_out) memcpy(status_out, it->st.data(), it->n);
+    txv_ctx* gctx = (!r && it->guard_failed) ? it->ctx : nullptr;
     if (!r && !it->upd) {
       if (p->recent.size() >= 8) p->recent.pop_front();
       p->recent.emplace_back(it->id, std::move(it->st));
     }
+    // a routed batch whose buffer did not carry the header its meta described: the statuses (all
+    // TXV_POOL_NOT_CHECKED) are out and kept, the pool is unchanged, the wait says so
+    if (gctx) r = txv_ctx_fail(gctx, TXV_EINVAL, "txv_pool_check_routed: the buffer's header differs from the meta (every vote not checked)");
     p->tickets.erase(it);
     prune_updates(p);
     pt.mark("finish");

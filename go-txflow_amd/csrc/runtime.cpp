@@ -19,6 +19,7 @@
 #include "host_pack.hpp"
 #include "sha2.h"
 #include "route.h"
+#include "routepool_dev.h"
 
 #include <hip/hip_runtime.h>
 #include <emmintrin.h>
@@ -74,6 +75,7 @@ constexpr uint32_t kIngestRing = 3;
 constexpr uint32_t kRouteSlot = kIngestSlot + kIngestRing;   // the route ring's columns: entry k in slot kRouteSlot + k
 constexpr uint32_t kRouteRing = TXV_ROUTE_RING;
 constexpr uint32_t kSlots = kRouteSlot + kRouteRing;
+constexpr uint32_t kRoutePoolRing = 2;   // key / size / valid columns of routed CheckTx batches (txv_ctx::rpool)
 
 struct Slot {
   uint32_t cap = 0, n = 0, n_pad = 0, msg_words = 0, msg_cap_words = 0;
@@ -348,6 +350,27 @@ struct txv_ctx {
   } route[kRouteRing];
   std::mutex route_mu;
   uint64_t route_next = 1;           // next route ticket; guarded by mu
+  // CheckTx from a route buffer (txv_pool_check_routed_submit; kernels_routepool.hip): a ring of the
+  // keys / sizes / valid columns txv_k_route_keys writes for the pool engine, sized by max_batch
+  // (like the ingest ring's d_keys / d_sizes).  An entry's kernel runs on the key stream, which has
+  // waited for the engine chain that read the entry before (pooldev_enqueue's then_stream), so an
+  // entry is rewritten only behind its last reader; ev ends its kernel.  Guarded by mu.  The guard
+  // words (mapped host memory, one per routed pool ticket until it is finished) are handed out in
+  // chunks under rp_mu
+  struct RoutePool {
+    uint32_t cap = 0;
+    uint32_t *d_keys = nullptr, *d_sizes = nullptr;
+    uint8_t* d_valid = nullptr;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+  } rpool[kRoutePoolRing];
+  uint64_t rpool_next = 0;
+  hipEvent_t rp_ks_ev = nullptr;     // the key stream as of a routed submit: the staging copies wait for it
+  uint8_t* d_rp_st = nullptr;        // host statuses of a waited pool ticket, for the nil column (copy stream)
+  uint32_t rp_st_cap = 0;
+  std::mutex rp_mu;
+  std::vector<std::pair<uint32_t*, uint32_t*>> rp_words;    // free guard words (host, device address)
+  std::vector<uint32_t*> rp_chunks;                          // their allocations
   // txv_sig_keys scratch: signatures [n][16] u32, lengths, keys [n][8] u32
   uint32_t pk_cap = 0;
   std::mutex pk_mu;                  // txv_sig_keys' buffers (not c->mu: CheckTx's keys run beside txv_submit_votes)
@@ -1674,6 +1697,13 @@ void txv_destroy(txv_ctx* c) {
     dfree(e.d_msg); dfree(e.d_msg_len); dfree(e.d_r); dfree(e.d_rpts); dfree(e.d_renc);
     for (hipEvent_t ev : {e.up_ev, e.ev0, e.ev}) if (ev) (void)hipEventDestroy(ev);
   }
+  for (auto& e : c->rpool) {
+    dfree(e.d_keys); dfree(e.d_sizes); dfree(e.d_valid);
+    if (e.ev) (void)hipEventDestroy(e.ev);
+  }
+  dfree(c->d_rp_st);
+  if (c->rp_ks_ev) (void)hipEventDestroy(c->rp_ks_ev);
+  for (uint32_t* w : c->rp_chunks) (void)hipHostFree(w);
   dfree(c->d_chain); dfree(c->d_chain_sign);
   dfree(c->d_pk_sig); dfree(c->d_pk_len); dfree(c->d_pk_keys); hfree(c->h_pk_sig); hfree(c->h_pk_len); hfree(c->h_pk_keys);
   dfree(c->d_wd_wire); hfree(c->h_wd_wire); dfree(c->d_wd_off); hfree(c->h_wd_off); dfree(c->d_wd_len); hfree(c->h_wd_len);
@@ -2984,6 +3014,13 @@ int sign_drain(txv_ctx* c) {
   return TXV_OK;
 }
 
+// the same for the routed CheckTx ring's key kernels (txv_pool_check_routed_submit)
+int routepool_drain(txv_ctx* c) {
+  for (auto& e : c->rpool)
+    if (e.used && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
+  return TXV_OK;
+}
+
 // A synchronous route (submit + wait in one call) that leaves the ring idle takes its entry again
 // next time: the next ticket is t + kRouteRing, on entry (t - 1) % kRouteRing like t.  A caller
 // that never pipelines then keeps to one entry's slot and scratch (one allocation, warm buffers),
@@ -3423,6 +3460,7 @@ int txv_reset_flow(txv_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (int r = route_drain(c)) return r;
   if (int r = sign_drain(c)) return r;
+  if (int r = routepool_drain(c)) return r;
   if (!c->n_vals) return TXV_OK;
   return reset_tally(c, false);
 }
@@ -3436,6 +3474,7 @@ int txv_sync(txv_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = route_drain(c)) return r;
     if (int r = sign_drain(c)) return r;
+    if (int r = routepool_drain(c)) return r;
   }
   HIP_TRY(c, hipStreamSynchronize(c->vstream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3744,6 +3783,17 @@ int txv_sign_txs_ms(txv_ctx* c, float* ms) {
   if (!c || !ms) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   *ms = c->sign_ms;
+  return TXV_OK;
+}
+
+int txv_sign_txs_meta(txv_ctx* c, uint32_t n, uint32_t signer, txv_route_meta* meta_out) {
+  if (!c || !meta_out) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->n_vals) { c->err = "no validator set"; return TXV_ESTATE; }
+  if (signer >= c->n_signers) { c->err = "signer is not a txv_keygen slot"; return TXV_EINVAL; }
+  if (n > c->cfg.max_batch) { c->err = "batch exceeds max_batch"; return TXV_EINVAL; }
+  const uint32_t m = signer_is_validator(c, signer) ? n : 0u;   // sign_submit's e.meta
+  *meta_out = txv_route_meta{m, m ? 64u : 0u, TXV_ROUTE_TXKEY, 0u, 64ull * m, txv_route_bytes(m, 64ull * m, TXV_ROUTE_TXKEY)};
   return TXV_OK;
 }
 
@@ -4578,6 +4628,7 @@ struct PoolDev {
     // the slot waits for it on the GPU)
     uint64_t occ = 0;
     uint32_t occ_upd = 0, occ_n = 0;
+    bool occ_routed = false;                       // a routed batch (txv_pool_check_routed_submit): statuses, no signatures
     hipEvent_t cons_ev = nullptr;
     bool cons = false;
   } fl[kPdRing];
@@ -5157,11 +5208,12 @@ int pooldev_finish(txv_ctx* c, PoolDev* s, int slot, const uint8_t** status, con
 
 // flight slot `slot` holds pool ticket `id`'s batch (n votes after n_upd Update entries): a TxFlow
 // chain may read its signatures and statuses from HBM (pooldev_consume) until the slot is reused
-void pooldev_set_occupant(PoolDev* s, int slot, uint64_t id, uint32_t n_upd, uint32_t n) {
+void pooldev_set_occupant(PoolDev* s, int slot, uint64_t id, uint32_t n_upd, uint32_t n, bool routed) {
   PoolDev::Flight& f = s->fl[slot];
   f.occ = id;
   f.occ_upd = n_upd;
   f.occ_n = n;
+  f.occ_routed = routed;
 }
 
 // txv_submit_checked: pool ticket `id`'s signatures ([n][64] bytes) into sig_out and its statuses
@@ -5173,10 +5225,14 @@ int pooldev_consume(txv_ctx* c, PoolDev* s, uint64_t id, uint32_t n, hipStream_t
   if (!s || !id) return 1;
   for (PoolDev::Flight& f : s->fl) {
     if (f.occ != id) continue;
+    // a routed batch's slot holds statuses but no signatures: a consumer that wants them takes the
+    // ticket's host statuses and its own columns instead
+    if (f.occ_routed && sig_out) return 1;
     if (f.occ_n != n) { c->err = "txv_submit_checked: the batch differs from the pool ticket's"; return TXV_EINVAL; }
     if (!f.cons_ev) HIP_TRY(c, hipEventCreateWithFlags(&f.cons_ev, hipEventDisableTiming));
     HIP_TRY(c, hipStreamWaitEvent(st, f.ev, 0));
-    HIP_TRY(c, hipMemcpyAsync(sig_out, f.d_sig + (size_t)f.occ_upd * 16, (size_t)n * 64, hipMemcpyDeviceToDevice, st));
+    if (sig_out)
+      HIP_TRY(c, hipMemcpyAsync(sig_out, f.d_sig + (size_t)f.occ_upd * 16, (size_t)n * 64, hipMemcpyDeviceToDevice, st));
     if (raw_status)   // the statuses themselves (txv_route_checked: the route kernels read TXV_POOL_*)
       HIP_TRY(c, hipMemcpyAsync(nil_out, f.d_status + f.occ_upd, n, hipMemcpyDeviceToDevice, st));
     else
@@ -5284,6 +5340,142 @@ int route_checked_consume(txv_ctx* c, PoolDev* dev, uint64_t pool_ticket, uint32
   // on the stream: the route's kernels run behind these reads, so behind the decisions)
   c->route[k].d_perr_src = dev->d_err;
   HIP_TRY(c, hipEventRecord(s.ev[3], ks));
+  return TXV_OK;
+}
+
+// ---- CheckTx and TryAddVote from a route buffer in HBM (pool.cpp drives these; include/txvote.h
+// txv_pool_check_routed_submit / txv_submit_routed_checked) ----
+
+// what both entry points check before they take a lock
+bool routepool_args_ok(const txv_ctx* c, const void* buf, const txv_route_meta* m) {
+  if (!c || !buf || !m || (uintptr_t)buf % 16) return false;
+  return m->bytes == txv_route_bytes(m->n, m->arena_bytes, m->flags) && m->n <= c->cfg.max_batch;
+}
+
+// a guard word (mapped host memory, zero) for a routed pool ticket: its host and device address
+int routepool_word_get(txv_ctx* c, uint32_t** h, uint32_t** m) {
+  std::lock_guard<std::mutex> g(c->rp_mu);
+  if (c->rp_words.empty()) {
+    constexpr size_t kChunk = 64;
+    uint32_t *hw = nullptr, *mw = nullptr;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = halloc_mapped(c, &hw, &mw, kChunk)) return r;
+    c->rp_chunks.push_back(hw);
+    for (size_t k = 0; k < kChunk; ++k) c->rp_words.emplace_back(hw + k, mw + k);
+  }
+  *h = c->rp_words.back().first;
+  *m = c->rp_words.back().second;
+  c->rp_words.pop_back();
+  **h = 0;
+  return TXV_OK;
+}
+void routepool_word_put(txv_ctx* c, uint32_t* h, uint32_t* m) {
+  std::lock_guard<std::mutex> g(c->rp_mu);
+  c->rp_words.emplace_back(h, m);
+}
+
+// the device path's first half: txv_k_route_keys over the buffer into the ring's next entry, on the
+// key stream (behind any sign chain of this context still writing the buffer: it ends there);
+// *after = the event that ends the kernel, *then_stream = the key stream (it waits for the engine
+// chain, so the entry's next kernel runs behind its reader)
+int routepool_keys(txv_ctx* c, const void* buf, const txv_route_meta* m, uint32_t* guard_m, const uint32_t** d_keys,
+                   const uint32_t** d_sizes, const uint8_t** d_valid, void** after, void** then_stream) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  txv_ctx::RoutePool& e = c->rpool[c->rpool_next % kRoutePoolRing];
+  int r;
+  if (!e.ev) HIP_TRY(c, hipEventCreateWithFlags(&e.ev, hipEventDisableTiming));
+  if (e.cap < m->n) {   // (hipFree waits for the device: the old columns' readers have ended)
+    const uint32_t cap = std::min<uint32_t>(c->cfg.max_batch, std::max<uint32_t>(m->n, 4096));
+    e.cap = 0;
+    if ((r = dalloc(c, &e.d_keys, (size_t)cap * 8)) || (r = dalloc(c, &e.d_sizes, cap)) || (r = dalloc(c, &e.d_valid, cap)))
+      return r;
+    e.cap = cap;
+  }
+  RouteKeysArgs a{};
+  a.buf = static_cast<const uint8_t*>(buf);
+  a.n = m->n; a.flags = m->flags; a.max_txhash_len = m->max_txhash_len;
+  a.arena_bytes = m->arena_bytes;
+  a.total = txv_route::layout(m->n, m->arena_bytes, m->flags, a.off);
+  a.keys = e.d_keys; a.sizes = e.d_sizes; a.valid = e.d_valid; a.err_host = guard_m;
+  HIP_TRY(c, txv_launch_route_keys(&a, c->key_stream));
+  HIP_TRY(c, hipEventRecord(e.ev, c->key_stream));
+  e.used = true;
+  ++c->rpool_next;
+  *d_keys = e.d_keys; *d_sizes = e.d_sizes; *d_valid = e.d_valid;
+  *after = (void*)e.ev;
+  *then_stream = (void*)c->key_stream;
+  return TXV_OK;
+}
+
+// the host path's read-out: the buffer's bytes, behind the key stream's work (a sign chain still
+// writing it); the one copy that blocks
+int routepool_readback(txv_ctx* c, const void* buf, uint64_t bytes, uint8_t* out) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(out, buf, bytes, hipMemcpyDeviceToHost, c->key_stream));
+  HIP_TRY(c, hipStreamSynchronize(c->key_stream));
+  return TXV_OK;
+}
+
+// txv_submit_routed_checked's context half, in three steps as txv_submit_checked's (sub_mu held by
+// the caller): the buffer's columns staged by stage_routed's copies behind the key stream's work so
+// far ...
+int submit_routed_checked_stage(txv_ctx* c, const void* buf, const txv_route_meta* m, uint32_t* slot_out) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t slot = (uint32_t)((c->next_ticket - 1) % kSubmitRing);
+  if (c->slots[slot].ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  if (!c->rp_ks_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->rp_ks_ev, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->rp_ks_ev, c->key_stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->rp_ks_ev, 0));
+  if (int r = stage_routed(c, slot, static_cast<const uint8_t*>(buf), m)) return r;
+  *slot_out = slot;
+  return TXV_OK;
+}
+
+// ... the nil column from the statuses in the engine's flight slot (the pool's lock held), or-ed
+// into the buffer's own when it has one; 1 = the batch is no longer in the engine ...
+int submit_routed_checked_consume(txv_ctx* c, uint32_t slot, PoolDev* dev, uint64_t pool_ticket, uint32_t n) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  Slot& s = c->slots[slot];
+  hipStream_t ks = c->key_stream;
+  HIP_TRY(c, hipStreamWaitEvent(ks, s.ev[3], 0));   // the staging copies (and the slot's previous chain)
+  const int r = pooldev_consume(c, dev, pool_ticket, n, ks, nullptr, s.d_nil, s.has_nil, false);
+  if (r) return r;
+  HIP_TRY(c, hipEventRecord(s.ev[3], ks));          // run_slot's streams wait for the columns here
+  return TXV_OK;
+}
+
+// ... or from the ticket's host statuses (host_st; null after a device consume), then the chain.
+// why 1 = unknown pool ticket, 2 = another batch size
+int submit_routed_checked_run(txv_ctx* c, uint32_t slot, uint32_t n, const uint8_t* host_st, int why, uint64_t* ticket) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (why == 1) { c->err = "txv_submit_routed_checked: unknown pool ticket (already waited?)"; return TXV_ESTATE; }
+  if (why == 2) { c->err = "txv_submit_routed_checked: the batch differs from the pool ticket's"; return TXV_EINVAL; }
+  Slot& s = c->slots[slot];
+  if (host_st && n) {
+    if (c->rp_st_cap < n) {
+      c->rp_st_cap = 0;
+      if (int r = dalloc(c, &c->d_rp_st, std::max<uint32_t>(n, 4096))) return r;
+      c->rp_st_cap = std::max<uint32_t>(n, 4096);
+    }
+    memcpy(s.h_nil, host_st, n);   // the slot is free: its pinned column is this call's
+    hipStream_t cs = c->copy_stream;   // behind the staging copies (and every earlier use of d_rp_st)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rp_st, s.h_nil, n, hipMemcpyHostToDevice, cs));
+    HIP_TRY(c, txv_launch_nil_from_status(c->d_rp_st, n, s.d_nil, s.has_nil ? 1u : 0u, cs));
+    HIP_TRY(c, hipEventRecord(s.ev[3], cs));
+  }
+  s.has_nil = true;
+  int r;
+  if ((r = run_slot(c, slot, nullptr))) return r;
+  const uint64_t t = c->next_ticket;
+  s.ticket = t;
+  s.u_ticket = t;
+  c->next_ticket = t + 1;
+  *ticket = t;
   return TXV_OK;
 }
 

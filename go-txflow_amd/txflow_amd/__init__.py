@@ -93,6 +93,16 @@ class GossipMsgsError(TxvInfraError):
         self.nbytes = nbytes
 
 
+class RouteGuardError(TxvInfraError):
+    """TxVotePool.check_wait / check_routed of a route buffer whose header was not the one its meta
+    described (TXV_EINVAL): the kernel touched nothing beyond the header and the pool is unchanged.
+    statuses = what the call wrote: POOL_NOT_CHECKED for every vote."""
+
+    def __init__(self, msg, statuses):
+        super().__init__(msg)
+        self.statuses = statuses
+
+
 class TxvCapacityError(TxvInfraError):
     """Context.route_wait / route_admitted / route_checked: a rank's buffer would not fit its stride
     (TXV_ECAPACITY).  metas = every rank's txv_route_meta: the refused ones have reserved = 1, their
@@ -278,6 +288,11 @@ def lib():
             "txv_sign_txs": ([vp, ctypes.POINTER(_Txs), u32, i64, vp, ctypes.c_uint64, vp], ctypes.c_int),
             "txv_sign_txs_ms": ([vp, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
             "txv_scalarmult_base": ([vp, vp, u32, vp], ctypes.c_int),
+            "txv_sign_txs_meta": ([vp, u32, u32, vp], ctypes.c_int),
+            "txv_pool_check_routed_submit": ([vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_pool_check_routed": ([vp, vp, vp, vp, vp], ctypes.c_int),
+            "txv_submit_routed_checked": ([vp, vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+                                          ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -311,7 +326,8 @@ EXPORTED_SYMBOLS = [
     "txv_store_sink_enable", "txv_store_records",
     "txv_gossip_sink_enable", "txv_gossip_msgs",
     "txv_sign_txs_bytes", "txv_sign_txs_submit", "txv_sign_txs_wait", "txv_sign_txs", "txv_sign_txs_ms",
-    "txv_scalarmult_base"]
+    "txv_scalarmult_base",
+    "txv_sign_txs_meta", "txv_pool_check_routed_submit", "txv_pool_check_routed", "txv_submit_routed_checked"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -794,6 +810,19 @@ class Context:
         self._inflight[t.value] = int(m[0]["n"])
         return t.value
 
+    def submit_routed_checked(self, buf_ptr: int, meta, pool, pool_ticket: int) -> int:
+        """txv_submit_routed_checked: TryAddVote for the route buffer (device address buf_ptr, in
+        this context's HBM) that TxVotePool.check_routed_submit(buf_ptr, meta) returned pool_ticket
+        for -- submit_routed with the votes the pool did not admit as nil entries, decided on the
+        device behind the pool's decisions while the ticket is in flight; a ticket for wait_votes"""
+        m = np.ascontiguousarray(np.asarray(meta, ROUTE_META_DTYPE).reshape(1))
+        t = ctypes.c_uint64()
+        self._chk(lib().txv_submit_routed_checked(self._h, ctypes.c_void_p(buf_ptr), m.ctypes.data, pool._h, pool_ticket,
+                                                  ctypes.byref(t)), "txv_submit_routed_checked")
+        self._inflight = getattr(self, "_inflight", {})
+        self._inflight[t.value] = int(m[0]["n"])
+        return t.value
+
     def submit_votes(self, batch: VoteBatch) -> int:
         """asynchronous TryAddVote batch (txv_submit_votes): returns a ticket for wait_votes"""
         t = ctypes.c_uint64()
@@ -1047,6 +1076,14 @@ class Context:
                                      meta.ctypes.data), "txv_sign_txs")
         return meta[0]
 
+    def sign_txs_meta(self, n: int, signer: int):
+        """txv_sign_txs_meta: the meta sign_txs_wait will return for n txs and this signer (n = 0 for
+        a signer outside the registry), to enqueue check_routed_submit / submit_routed_checked behind
+        an unwaited sign_txs_submit"""
+        meta = np.zeros(1, ROUTE_META_DTYPE)
+        self._chk(lib().txv_sign_txs_meta(self._h, n, signer, meta.ctypes.data), "txv_sign_txs_meta")
+        return meta[0]
+
     def sign_txs_ms(self) -> float:
         """device time (ms) of the last waited sign chain"""
         ms = ctypes.c_float()
@@ -1277,6 +1314,13 @@ SUBMIT_RING = 4         # txv_submit_votes batches in flight (staged slots 0 .. 
 POOL_DEVICE_CACHE = 0x2   # TXV_POOL_DEVICE_CACHE: the LRU cache in HBM, CheckTx decisions on the GPU
 
 
+class _RoutedBatch:
+    """what TxVotePool keeps for a routed ticket until its wait: the batch's size"""
+
+    def __init__(self, n: int):
+        self.n = n
+
+
 class TxVotePool:
     """TxVotePool (txvotepool/txvotepool.go) over libtxvote.so: CheckTx (:180-261) per vote in
     arrival order with the txVoteKey = SHA-256(Signature) keys computed on the GPU of `ctx`,
@@ -1337,14 +1381,47 @@ class TxVotePool:
         return t.value
 
     def check_wait(self, ticket: int) -> np.ndarray:
-        """txv_pool_check_wait: the statuses of a submitted batch"""
+        """txv_pool_check_wait: the statuses of a submitted batch (RouteGuardError, with the
+        statuses, for a routed batch whose buffer's header was not its meta's)"""
         batch = self._inflight[ticket][0]
-        out = np.zeros(max(batch.n, 1), np.uint8)
+        out = np.full(max(batch.n, 1), POOL_NOT_CHECKED if isinstance(batch, _RoutedBatch) else 0, np.uint8)
         rc = lib().txv_pool_check_wait(self._h, ticket, out.ctypes.data)
         del self._inflight[ticket]
+        if rc == -22 and isinstance(batch, _RoutedBatch):
+            raise RouteGuardError(f"txv_pool_check_wait failed ({rc}): {lib().txv_last_error(self.ctx._h).decode()}",
+                                  out[:batch.n])
         if rc != 0:
             raise TxvInfraError(f"txv_pool_check_wait failed ({rc})")
         return out[:batch.n]
+
+    def check_routed_submit(self, buf_ptr: int, meta) -> int:
+        """txv_pool_check_routed_submit: CheckTx for every vote of the route buffer at device address
+        buf_ptr (in ctx's HBM; meta as Context.submit_routed takes it), in buffer order; with the
+        device cache nothing waits for the GPU or crosses the link.  A ticket for check_wait.  The
+        buffer must stay unchanged until the wait."""
+        ctx = self._ctx_or_raise("check_routed_submit")
+        m = np.ascontiguousarray(np.asarray(meta, ROUTE_META_DTYPE).reshape(1))
+        t = ctypes.c_uint64(0)
+        ctx._chk(lib().txv_pool_check_routed_submit(self._h, ctx._h, ctypes.c_void_p(buf_ptr), m.ctypes.data,
+                                                    ctypes.byref(t)), "txv_pool_check_routed_submit")
+        if not hasattr(self, "_inflight"):
+            self._inflight = {}
+        self._inflight[t.value] = (_RoutedBatch(int(m[0]["n"])),)
+        return t.value
+
+    def check_routed(self, buf_ptr: int, meta) -> np.ndarray:
+        """txv_pool_check_routed: check_routed_submit + check_wait in one call"""
+        ctx = self._ctx_or_raise("check_routed")
+        m = np.ascontiguousarray(np.asarray(meta, ROUTE_META_DTYPE).reshape(1))
+        n = int(m[0]["n"])
+        out = np.full(max(n, 1), POOL_NOT_CHECKED, np.uint8)
+        rc = lib().txv_pool_check_routed(self._h, ctx._h, ctypes.c_void_p(buf_ptr), m.ctypes.data, out.ctypes.data)
+        if rc == -22:
+            msg = lib().txv_last_error(ctx._h).decode()
+            if "header differs" in msg:
+                raise RouteGuardError(f"txv_pool_check_routed failed ({rc}): {msg}", out[:n])
+        ctx._chk(rc, "txv_pool_check_routed")
+        return out[:n]
 
     def prepare(self, batch: VoteBatch, long_sigs: Optional[dict] = None):
         """txv_pool_prepare: (keys [n, 32] u8, TxVote.Size() [n] u32) of a batch -- the

@@ -44,6 +44,10 @@
  *   txv_sign_txs_submit / txv_sign_txs_wait <- Reactor.signTxRoutine's body for a batch of txs,
  *                         txvotepool/reactor.go:108-126: NewTxVote types/tx_vote.go:57-71 +
  *                         privVal.SignTxVote types/priv_validator.go:83-95, into a route buffer
+ *   txv_pool_check_routed_submit / txv_submit_routed_checked <- the rest of signTxRoutine and what
+ *                         follows it: txVotePool.CheckTx(txVote) txvotepool/reactor.go:126 ->
+ *                         txvotepool.go:180-261, then checkMaj23Routine -> TryAddVote, from that
+ *                         route buffer where it lies in HBM
  */
 #ifndef TXVOTE_H
 #define TXVOTE_H
@@ -575,6 +579,12 @@ int txv_sign_txs(txv_ctx* ctx, const txv_txs* txs, uint32_t signer, int64_t heig
                  txv_route_meta* meta_out);
 /* measurement: device time (ms) of the last waited sign chain, by events on the stream it ran on */
 int txv_sign_txs_ms(txv_ctx* ctx, float* ms);
+/* the meta txv_sign_txs_wait will return for n txs and this signer (n = 0 for a signer outside the
+ * registry: "only sign if I'm a validator", txvotepool/reactor.go:111), so that
+ * txv_pool_check_routed_submit and txv_submit_routed_checked can be enqueued behind an unwaited
+ * txv_sign_txs_submit.  TXV_ESTATE without a validator set, TXV_EINVAL when signer is not a slot or
+ * n > max_batch. */
+int txv_sign_txs_meta(txv_ctx* ctx, uint32_t n, uint32_t signer, txv_route_meta* meta_out);
 /* measurement / self-test only, like txv_fe_selftest: enc_out[i] = canonical encoding of
  * [scalars32[i]]B through the signer's walk and encode kernels (scalars little-endian, any 256-bit
  * value below 2^253; TXV_EINVAL above, TXV_ESTATE without a validator set) */
@@ -679,6 +689,67 @@ int txv_pool_check_wait(txv_pool* pool, uint64_t ticket, uint8_t* status_out);
  * ticket is still waited by the caller (txv_pool_check_wait, before or after this call).  Takes
  * the pool's lock, then the context's. */
 int txv_submit_checked(txv_ctx* ctx, const txv_votes* votes, txv_pool* pool, uint64_t pool_ticket, uint64_t* ticket);
+/* ---- CheckTx and TryAddVote from a route buffer in HBM: a validator's own votes stay on the device ----
+ * <- txVotePool.CheckTx(txVote) of signTxRoutine (txvotepool/reactor.go:126 -> txvotepool.go:180-261)
+ * for every vote of a route buffer in ctx's HBM (what txv_sign_txs_submit wrote, or any buffer of
+ * the txv_route_admitted layout), in buffer order.  The pool ticket is an ordinary one:
+ * txv_pool_check_wait collects it, it orders with every other CheckTx and Update submission, and
+ * txv_pool_update_fired, txv_pool_sync, reap and the cache reads behave as after
+ * txv_pool_check_submit.  Statuses and pool state equal txv_pool_check on the txv_route_view of a
+ * host copy of the buffer, but for two classes of vote that call refuses wholesale and a buffer in
+ * HBM cannot be inspected for before the submit returns; both get TXV_POOL_NOT_CHECKED and never
+ * touch the pool: a vote whose TXV_ROUTE_NIL byte is set (a nil *TxVote never reaches CheckTx) and
+ * a vote with sig_len > 64 (the buffer carries only its first 64 bytes, so its key cannot be
+ * formed).  addr_len > 20 is not special: CheckTx never looks at the address and Size() uses the
+ * length as given.
+ *
+ * With TXV_POOL_DEVICE_CACHE, the engine on ctx's GPU and caps that cannot bind (n pushes of the
+ * largest Size() a vote with max_txhash_len, a 20-byte address and a 64-byte signature can have,
+ * beside the batches in flight) nothing waits for the GPU and nothing crosses the link: one kernel
+ * reads the buffer into the keys, sizes and validity the engine decides from.  Every other pool
+ * (no TXV_POOL_DEVICE_CACHE, an engine on another GPU, caps that may bind) reads the buffer
+ * back -- one copy, the only case that blocks -- and runs the host admission; the results are the
+ * same in every mode.
+ *
+ * The submit cannot read the buffer's header, so the kernel does: unless magic, n, arena_bytes,
+ * flags, max_txhash_len and total bytes all equal the meta's it touches nothing beyond the header,
+ * every vote is TXV_POOL_NOT_CHECKED, the pool is unchanged, and txv_pool_check_wait writes those
+ * statuses and returns TXV_EINVAL (txv_last_error(ctx) says why).  A meta must still never describe
+ * more bytes than the allocation holds.
+ *
+ * TXV_EINVAL from the call itself: a null argument, buf_dev not 16-byte aligned, meta->bytes !=
+ * txv_route_bytes(meta->n, meta->arena_bytes, meta->flags), n > max_batch.  n == 0 is a valid empty
+ * batch: a pool ticket with zero statuses.
+ *
+ * Ordering and lifetime: the kernel (and txv_submit_routed_checked's staging copies) are enqueued
+ * behind any txv_sign_txs_submit chain of the same context that is still writing the buffer, so
+ * sign_submit -> check_routed_submit -> submit_routed_checked may be issued back to back with
+ * txv_sign_txs_meta's meta and the three waits may follow in any order.  The buffer must stay
+ * unchanged until both the pool ticket and the flow ticket are waited (the rule of registered
+ * memory in txv_pool_check_submit).  txv_sync, txv_reset_flow and txv_destroy wait for the kernels
+ * in flight first. */
+int txv_pool_check_routed_submit(txv_pool* pool, txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta,
+                                 uint64_t* pool_ticket);
+/* submit + txv_pool_check_wait */
+int txv_pool_check_routed(txv_pool* pool, txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta,
+                          uint8_t* status_out);
+/* <- checkMaj23Routine -> TryAddVote (txflow/service.go:123-166) for the batch that pool_ticket
+ * (txv_pool_check_routed_submit on the same buffer) is deciding: txv_submit_routed with the votes
+ * the pool did not admit as nil entries, the counterpart of txv_submit_checked.  A txv_submit_votes
+ * ticket for txv_wait_votes from the same submit ring (four in flight, TXV_ESTATE beyond); the
+ * gossip, store and Update sinks see the batch as they see any other.  While the pool ticket is in
+ * the engine's flight slot the columns are staged by device-to-device copies, the nil column is
+ * built on the device from the slot's statuses (or-ed into the buffer's own nil column when it has
+ * one) and the chain runs behind the decisions with no host round trip; otherwise the ticket's
+ * statuses are taken on the host, as txv_submit_checked does (TXV_ESTATE for an unknown ticket,
+ * TXV_EINVAL for a batch of another size).  On a ticket whose buffer failed the header check it
+ * runs a batch of nil entries.  Takes the submit lock, then the pool's, then the context's.
+ *
+ * The flight slot of a routed ticket holds statuses but no signatures: txv_submit_checked and
+ * txv_route_submit_checked given such a ticket take its statuses on the host and the signatures
+ * from the caller's columns. */
+int txv_submit_routed_checked(txv_ctx* ctx, const void* buf_dev, const txv_route_meta* meta, txv_pool* pool,
+                              uint64_t pool_ticket, uint64_t* ticket);
 /* CheckTxWithInfo for n votes given as (txVoteKey, TxVote.Size()) pairs in arrival order: keys32
  * n x 32 bytes (SHA-256(Signature), txvotepool.go:467-469), sizes[i] = Size() (0 when amino
  * rejects the timestamp); status_out[i] = TXV_POOL_*.  ctx (optional) lends its host workers;
