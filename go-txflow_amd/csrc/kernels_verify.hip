@@ -21,6 +21,7 @@
 
 #include "ed25519_dev.h"
 #include "fe_inv_var.h"
+#include "signbytes_dev.h"
 #include "txv_device.h"
 #include "walk_lds.h"
 
@@ -112,7 +113,10 @@ __device__ __forceinline__ uint32_t tab_slot(const VerifyArgs& a, uint32_t v) { 
 
 // Prechecks + challenge of vote i: false if the vote is rejected before the group equation
 // (length, sig[63] & 0xE0, undecodable A, s >= L, SignBytes failure), else k = SHA-512(R||A||M)
-// mod L and the S half of the signature.
+// mod L and the S half of the signature.  FIELDS: M comes from the vote's field columns
+// (a.msg == null), else from the message buffer; a kernel of its own for each, so that neither
+// pays for the other's registers.
+template <bool FIELDS = false>
 __device__ __forceinline__ bool vote_challenge(const VerifyArgs& a, uint32_t i, uint32_t k_out[8], uint32_t s_out[8]) {
   const uint8_t fl = a.flags[i];
   const uint32_t v = a.val[i];
@@ -129,13 +133,33 @@ __device__ __forceinline__ bool vote_challenge(const VerifyArgs& a, uint32_t i, 
     pre[j] = be64_from_le32(s[2 * j], s[2 * j + 1]);
     pre[4 + j] = be64_from_le32(pw[2 * j], pw[2 * j + 1]);
   }
-  MsgView m{a.msg + i, a.n_pad, a.msg_words, a.msg_len[i]};
   uint32_t dig[16];
+  if constexpr (!FIELDS) {
+    MsgView m{a.msg + i, a.n_pad, a.msg_words, a.msg_len[i]};
 #if TXV_K1A_PREFETCH
-  sha512_prefixed_pf(dig, pre, 8, m);
+    sha512_prefixed_pf(dig, pre, 8, m);
 #else
-  sha512_prefixed(dig, pre, 8, m);
+    sha512_prefixed(dig, pre, 8, m);
 #endif
+  } else {
+    // no message buffer: the blocks come from the vote's field columns (signbytes_dev.h).  The
+    // builder is chosen per wave: the compile-time layout when every hashing lane has the same
+    // common shape, else the per-lane gather
+    const VoteFields f{a.height[i], a.ts_sec[i], a.ts_nanos[i], a.txhash_len[i], a.txhash + a.txhash_off[i],
+                       a.chain_field, a.chain_field_len};
+    uint64_t st[8];
+    sha512_init(st);
+    const bool all64 = __all(fields_fast_ok<64>(f)), all32 = __all(fields_fast_ok<32>(f));
+    if (all64 || all32) {
+      uint64_t w[32];
+      if (all64) fields_blocks_fast<64>(w, pre, f);
+      else fields_blocks_fast<32>(w, pre, f);
+      sha512_two_blocks(st, w);
+    } else {
+      sha512_fields_generic(st, pre, f, nullptr);
+    }
+    sha512_digest_le(dig, st);
+  }
   sc k = sc_reduce512(dig);
 #pragma unroll
   for (int j = 0; j < 8; ++j) { k_out[j] = k.v[j]; s_out[j] = s[8 + j]; }
@@ -172,6 +196,7 @@ __device__ __forceinline__ bool vote_checks(const VerifyArgs& a, uint32_t i, uin
 __global__ void __launch_bounds__(256, 2) txv_k_challenge2(VerifyArgs a) {
   const uint32_t half = (a.n + 1) / 2;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (a.k1a_zeroes_wctr && blockIdx.x == 0 && threadIdx.x < 8 * 16) a.wctr[threadIdx.x] = 0;
   if (t >= half) return;
   const uint32_t i0 = t, i1 = t + half;
   const bool has1 = i1 < a.n;
@@ -214,15 +239,25 @@ __global__ void __launch_bounds__(256, 2) txv_k_challenge2(VerifyArgs a) {
 #else
 #define TXV_K1A_VGPR_ATTR
 #endif
-__global__ void __launch_bounds__(256, TXV_K1A_WAVES) TXV_K1A_VGPR_ATTR txv_k_challenge(VerifyArgs a) {
+template <bool FIELDS>
+__device__ __forceinline__ void challenge_body(const VerifyArgs& a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  // K1b's claim counters, when it follows on this stream (no launch of their own)
+  if (a.k1a_zeroes_wctr && blockIdx.x == 0 && threadIdx.x < 8 * 16) a.wctr[threadIdx.x] = 0;
   if (i >= a.n) return;
   if (!(a.flags[i] & TXV_FLAG_PENDING)) { a.ok_out[i] = 0; return; }   // K1b may walk every vote
   uint32_t k[8], s[8];
-  if (!vote_challenge(a, i, k, s)) { a.ok_out[i] = 0; return; }
+  if (!vote_challenge<FIELDS>(a, i, k, s)) { a.ok_out[i] = 0; return; }
 #pragma unroll
   for (int j = 0; j < 8; ++j) a.kbuf[(size_t)j * a.n_pad + i] = k[j];
   a.ok_out[i] = 2;   // passed the scalar checks; K1b decides
+}
+__global__ void __launch_bounds__(256, TXV_K1A_WAVES) TXV_K1A_VGPR_ATTR txv_k_challenge(VerifyArgs a) {
+  challenge_body<false>(a);
+}
+// the same without a message buffer (a.msg == null): SignBytes from the field columns
+__global__ void __launch_bounds__(256, TXV_K1A_WAVES) TXV_K1A_VGPR_ATTR txv_k_challenge_fields(VerifyArgs a) {
+  challenge_body<true>(a);
 }
 
 template <int W, typename PtrB>
@@ -1323,8 +1358,10 @@ static hipError_t launch_multi(const VerifyArgs* args, uint32_t grid, hipStream_
   } else if (args->lane_votes == 8) {
     if constexpr (WB >= 24) {
       if (TXV_K1B_DYNAMIC && args->wctr) {
-        const hipError_t e = hipMemsetAsync(args->wctr, 0, 8 * 16 * sizeof(uint32_t), st);
-        if (e != hipSuccess) return e;
+        if (!args->k1a_zeroes_wctr) {   // else K1a, the launch before this one on st, has zeroed them
+          const hipError_t e = hipMemsetAsync(args->wctr, 0, 8 * 16 * sizeof(uint32_t), st);
+          if (e != hipSuccess) return e;
+        }
         if constexpr (TXV_K1B_DYN_WAVES >= 3) {
           // persistent: every resident slot (256-thread blocks, TXV_K1B_DYN_WAVES per SIMD)
           // TXV_K1B_DYN_BLOCKS = blocks per CU x 100 (default: every slot); fewer leave SIMDs with
@@ -1403,7 +1440,10 @@ bool txv_k1b_fusable(int wb, const VerifyArgs* args) {
 hipError_t txv_launch_challenge(const VerifyArgs* args, hipStream_t st) {
   if (!args->n) return hipSuccess;
   static const bool pair = getenv("TXV_K1A_PAIR") && atoi(getenv("TXV_K1A_PAIR")) == 1;
-  if (pair) {
+  if (!args->msg) {   // (the paired experiment reads the message buffer)
+    if (!args->chain_field || !args->chain_field_len) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(txv_k_challenge_fields, dim3((args->n + 255) / 256), dim3(256), 0, st, *args);
+  } else if (pair) {
     const uint32_t half = (args->n + 1) / 2;
     hipLaunchKernelGGL(txv_k_challenge2, dim3((half + 255) / 256), dim3(256), 0, st, *args);
   } else {

@@ -18,6 +18,7 @@
 #include "amino.hpp"
 #include "host_pack.hpp"
 #include "sha2.h"
+#include "signbytes_dev.h"
 #include "route.h"
 #include "routepool_dev.h"
 
@@ -62,6 +63,18 @@ inline bool valid_window(int w) {
 // no longer add up to the verify time; off: K1a then K1b on the verify stream
 #ifndef TXV_K1A_ON_KEY_STREAM
 #define TXV_K1A_ON_KEY_STREAM 0
+#endif
+// TXV_K1A_FIELDS=1: run_slot launches no txv_k_signbytes; K1a builds R || A || SignBytes in
+// registers from the field columns (signbytes_dev.h).  0: the SignBytes go through the slot's
+// message buffer (one launch, one write and one read of msg_words x n_pad words per batch)
+#ifndef TXV_K1A_FIELDS
+#define TXV_K1A_FIELDS 1
+#endif
+// TXV_K1A_WCTR=1 (experiment): K1a zeroes K1b's claim counters when it runs just before K1b on the
+// verify stream (not on the key stream, not fused) instead of a hipMemsetAsync between the two.
+// No gain that could be told from the runs' spread (measured dead ends): off
+#ifndef TXV_K1A_WCTR
+#define TXV_K1A_WCTR 0
 #endif
 constexpr uint32_t kStagedSlots = 4;   // 0-3 staged (0-2 also the submit ring)
 constexpr uint32_t kSubmitRing = 4;    // txv_submit_votes batches in flight
@@ -209,6 +222,8 @@ struct txv_ctx {
   std::string chain;
   uint8_t* d_chain = nullptr; uint32_t d_chain_cap = 0;             // chain id for txv_k_signbytes
   uint8_t* d_chain_sign = nullptr; uint32_t d_chain_sign_cap = 0;   // txv_sign_votes' chain id
+  uint8_t* d_chain_field = nullptr; uint32_t d_chain_field_cap = 0; // K1a's chain field (signbytes_dev.h), padded
+  uint32_t chain_field_len = 0;                                     // with its 0x80
   std::unordered_map<std::string, uint32_t> addr_index;
   txv_host::AddrTable addr_tab;    // same map, lock-free reads for the parallel pack
   uint32_t* d_pubs = nullptr; uint8_t* d_decode_ok = nullptr; uint32_t* d_atables = nullptr;
@@ -840,6 +855,32 @@ int upload_chain(txv_ctx* c, const char* chain, uint32_t len, uint8_t** d, uint3
   return TXV_OK;
 }
 
+// the context's ChainID field as K1a's field builder reads it (signbytes_dev.h): the amino field
+// [0x2a uvarint(len) ChainID] (nothing for an empty id), SHA-512's 0x80 pad byte behind it, and
+// kChainFieldPad zero bytes on both sides
+int upload_chain_field(txv_ctx* c) {
+  const uint32_t len = (uint32_t)c->chain.size();
+  std::vector<uint8_t> h(txv::kChainFieldPad, 0);
+  if (len) {
+    uint8_t uv[10];
+    const uint32_t k = (uint32_t)txv_host::put_uvarint(uv, len);
+    h.push_back(0x2a);
+    h.insert(h.end(), uv, uv + k);
+    h.insert(h.end(), c->chain.begin(), c->chain.end());
+  }
+  h.push_back(0x80);
+  c->chain_field_len = (uint32_t)h.size() - txv::kChainFieldPad;
+  h.resize(h.size() + txv::kChainFieldPad, 0);
+  if (h.size() > c->d_chain_field_cap) {
+    int r;
+    if ((r = dalloc(c, &c->d_chain_field, h.size()))) return r;
+    c->d_chain_field_cap = (uint32_t)h.size();
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->d_chain_field, h.data(), h.size(), hipMemcpyHostToDevice, c->copy_stream));
+  HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+  return TXV_OK;
+}
+
 // Bound on the SignBytes length of any vote whose TxHash has at most max_hl bytes (the verify
 // kernels' message-column count): length prefix + Height (9) + TxHash field + TxKey (34) +
 // Timestamp field (<= 19) + ChainID field
@@ -1199,8 +1240,19 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   // TXV_K1B_FUSED=1 (experiment): the work-stealing K1b computes each chunk's challenges itself
   static const bool fuse = getenv("TXV_K1B_FUSED") && atoi(getenv("TXV_K1B_FUSED")) == 1;
   va.fused_k1a = fuse && txv_k1b_fusable(c->b_w, &va) ? 1u : 0u;
+  // no message buffer: K1a reads the field columns itself (the fused K1b experiment reads the buffer)
+  const bool k1a_fields = TXV_K1A_FIELDS && !va.fused_k1a;
+  if (k1a_fields) {
+    if (!c->d_chain_field && (r = upload_chain_field(c))) return r;
+    va.msg = nullptr;
+    va.height = sa.height; va.ts_sec = sa.ts_sec; va.ts_nanos = sa.ts_nanos;
+    va.txhash_off = sa.txhash_off; va.txhash_len = sa.txhash_len; va.txhash = sa.txhash;
+    va.chain_field = c->d_chain_field + txv::kChainFieldPad; va.chain_field_len = c->chain_field_len;
+  }
+  // TXV_K1A_WCTR: K1a, then K1b on the verify stream: K1a's first block zeroes K1b's claim counters
+  va.k1a_zeroes_wctr = TXV_K1A_WCTR && !TXV_K1A_ON_KEY_STREAM && !va.fused_k1a && va.wctr ? 1u : 0u;
   HIP_TRY(c, txv_flow_prep(&fs, &fb, ps));
-  HIP_TRY(c, txv_launch_signbytes(&sa, ps));
+  if (!k1a_fields) HIP_TRY(c, txv_launch_signbytes(&sa, ps));
   if (TXV_K1A_ON_KEY_STREAM && !va.fused_k1a) {
     HIP_TRY(c, hipEventRecord(s.ev[8], ps));
     HIP_TRY(c, txv_launch_challenge(&va, ps));
@@ -1704,7 +1756,7 @@ void txv_destroy(txv_ctx* c) {
   dfree(c->d_rp_st);
   if (c->rp_ks_ev) (void)hipEventDestroy(c->rp_ks_ev);
   for (uint32_t* w : c->rp_chunks) (void)hipHostFree(w);
-  dfree(c->d_chain); dfree(c->d_chain_sign);
+  dfree(c->d_chain); dfree(c->d_chain_sign); dfree(c->d_chain_field);
   dfree(c->d_pk_sig); dfree(c->d_pk_len); dfree(c->d_pk_keys); hfree(c->h_pk_sig); hfree(c->h_pk_len); hfree(c->h_pk_keys);
   dfree(c->d_wd_wire); hfree(c->h_wd_wire); dfree(c->d_wd_off); hfree(c->h_wd_off); dfree(c->d_wd_len); hfree(c->h_wd_len);
   dfree(c->d_wd_out); hfree(c->h_wd_out); dfree(c->d_wd_span); hfree(c->h_wd_span);
@@ -1908,7 +1960,7 @@ int txv_set_validators(txv_ctx* c, const uint8_t* pubs32, const int64_t* powers,
   c->chain.assign(chain_id ? chain_id : "", chain_id ? chain_len : 0);
   {
     int rr = upload_chain(c, c->chain.data(), (uint32_t)c->chain.size(), &c->d_chain, &c->d_chain_cap);
-    if (rr) return rr;
+    if (rr || (rr = upload_chain_field(c))) return rr;
   }
   int r;
   const int w = choose_window(c, n);

@@ -44,6 +44,17 @@ struct VerifyArgs {
   uint32_t n_cus;              // CUs of the context's device
   uint32_t fused_k1a;          // TXV_K1B_FUSED: the work-stealing K1b computes the challenges itself (no K1a)
   const uint32_t* tslot;       // [n_vals] table slot of each validator in atables, or null (slot = index)
+  // msg == null: K1a builds R || A || SignBytes in registers from the TxVote field columns
+  // (signbytes_dev.h) and reads no message buffer; msg_words and msg_len are then unused
+  const int64_t* height;       // [n]
+  const int64_t* ts_sec;       // [n]
+  const int32_t* ts_nanos;     // [n]
+  const uint32_t* txhash_off;  // [n] into txhash
+  const uint32_t* txhash_len;  // [n]
+  const uint8_t* txhash;       // TxHash arena (>= 16 bytes of padding behind it)
+  const uint8_t* chain_field;  // [0x2a uvarint(len) ChainID] 0x80, kChainFieldPad zero bytes around it
+  uint32_t chain_field_len;    // with the 0x80
+  uint32_t k1a_zeroes_wctr;    // K1a precedes K1b on its stream and zeroes wctr: K1b's launch skips the memset
 };
 
 #define TXV_PARK_WORDS 33          // X, Y, prefix product, Z of one parked vote; its vote index + 1
