@@ -66,7 +66,10 @@ extern "C" hipError_t txv_launch_sig_keys(const uint32_t* sig, const uint32_t* s
 // full keys are compared inside a run), cached keys from the cache's index.
 #include <hipcub/hipcub.hpp>
 #include "pool_dev.h"
+#include "senders_dev.h"
 #include "../../include/txvote.h"
+
+extern "C" hipError_t txv_senders_batch(const SendersArgs* a, hipStream_t st);   // kernels_senders.hip
 
 namespace {
 
@@ -91,7 +94,7 @@ __device__ __forceinline__ bool key_eq2(const uint32_t* ka, uint32_t a, const ui
 // derived seed each), never through a raw key slice: the keys are SHA-256 of peer-supplied
 // signature bytes that CheckTx never verifies (txvotepool.go:467-469), so a peer could grind keys
 // onto one home slot or one sort slice and make every probe or run scan of the batch quadratic.
-constexpr uint64_t kSeedIdx = 0x243F6A8885A308D3ull, kSeedList = 0x13198A2E03707344ull, kSeedSort = 0xA4093822299F31D0ull;
+constexpr uint64_t kSeedIdx = 0x243F6A8885A308D3ull, kSeedSort = 0xA4093822299F31D0ull;   // (kSeedList: pool_dev.h)
 __device__ __forceinline__ uint32_t idx_hash(const uint32_t* k, uint64_t seed) {
   return (uint32_t)txv_hash::key32(k, seed ^ kSeedIdx);
 }
@@ -586,8 +589,10 @@ extern "C" hipError_t txv_launch_nil_from_status(const uint8_t* st, uint32_t n, 
   return hipGetLastError();
 }
 
-// the whole decision + cache update chain for one batch on stream st (a.n > 0; a.C > 0 or 0)
-extern "C" hipError_t txv_pooldev_run(const PoolDevArgs* ap, hipStream_t st) {
+// the whole decision + cache update chain for one batch on stream st (a.n > 0; a.C > 0 or 0).
+// sn (TXV_POOL_SENDERS with the list in HBM, else null: no launch is added): the batch's Senders
+// pass, after pd_status and before the launch that indexes the batch's appends
+extern "C" hipError_t txv_pooldev_run(const PoolDevArgs* ap, const SendersArgs* sn, hipStream_t st) {
   const PoolDevArgs& a = *ap;
   const uint32_t n = a.n;
   if (!n) return hipSuccess;
@@ -608,6 +613,7 @@ extern "C" hipError_t txv_pooldev_run(const PoolDevArgs* ap, hipStream_t st) {
   }
   const uint32_t span = std::max(n, a.C);
   hipLaunchKernelGGL(pd_status, dim3(nt + ntc), b, 0, st, a);
+  if (sn && (e = txv_senders_batch(sn, st))) return e;
   if (!a.C) hipLaunchKernelGGL(pd_finish_nocache, gn, b, 0, st, a);
   else hipLaunchKernelGGL(pd_newcache, dim3((span + 255) / 256), b, 0, st, a);
   return hipGetLastError();

@@ -16,12 +16,14 @@
 //   4. addTx (:265-270): txs.PushBack, txsMap[key] = element, txsBytes += Size()
 // Update (:329-359) pushes every committed key to the cache and removes the pool element
 // txsMap[key] (removeTx :275-284, which subtracts the *committed* vote's Size()).
-// Sender bookkeeping (MempoolTxVote.Senders), the WAL and metrics carry no verdicts and are
-// not restated.
+// Sender bookkeeping (MempoolTxVote.Senders, :364-371) is kept only by a pool made with
+// TXV_POOL_SENDERS (senders_dev.h: one set of (entry, sender) words beside the list); the WAL and
+// metrics carry no verdicts and are not restated.
 #include "../../include/txvote.h"
 #include "amino.hpp"
 #include "txv_hash.h"
 #include "routepool_dev.h"
+#include "senders_dev.h"
 #include <random>
 
 #include <chrono>
@@ -287,26 +289,31 @@ struct PoolDev;
 void pooldev_free(PoolDev* s);
 bool pooldev_same_device(const txv_ctx* c, const PoolDev* s);
 uint32_t pooldev_cap(const PoolDev* s);
-int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n);
+int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n, bool senders);
 int pooldev_put_cache(txv_ctx* c, PoolDev* s, const uint8_t* keys, uint32_t L);
 int pooldev_get_cache(txv_ctx* c, PoolDev* s, std::vector<uint8_t>& keys);
 int pooldev_check(txv_ctx* c, PoolDev* s, const txv_votes* v, const uint8_t* h_keys_in, const uint32_t* h_sizes,
                   const uint32_t* d_keys, const uint32_t* d_sizes, const uint8_t* d_valid, uint32_t valid_ok, uint32_t n,
                   int64_t max_tx, bool wal, uint8_t* keys_out, uint8_t* status_out, void* after, bool list_on,
-                  uint64_t live_ub, int slot, uint32_t n_upd);
+                  uint64_t live_ub, int slot, uint32_t n_upd, const uint16_t* h_senders = nullptr);
 int pooldev_enqueue(txv_ctx* c, PoolDev* s, int slot, const txv_votes* v, const uint8_t* h_keys_in,
                     const uint32_t* h_sizes, const uint32_t* d_keys, const uint32_t* d_sizes, const uint8_t* d_valid,
                     uint32_t valid_ok, uint32_t n, int64_t max_tx, bool wal, bool keys_back, void* after_ev,
                     bool list_on, uint64_t live_ub, uint32_t n_upd, uint8_t* d_status_copy = nullptr,
-                    void* then_stream = nullptr);
+                    void* then_stream = nullptr, const uint16_t* h_senders = nullptr);
 int pooldev_stage(txv_ctx* c, PoolDev* s, int slot, uint32_t off, const txv_votes* v, const uint32_t* h_sizes);
 int pooldev_stage_dev(txv_ctx* c, PoolDev* s, int slot, uint32_t off, uint64_t ticket, uint32_t n);
 int update_list_keys(txv_ctx* c, uint64_t ticket, uint32_t n, std::vector<uint8_t>& keys, std::vector<uint32_t>& sizes);
 void pooldev_list_hint(PoolDev* s, uint64_t entries);
 int pooldev_finish(txv_ctx* c, PoolDev* s, int slot, const uint8_t** status, const uint8_t** keys, const uint32_t** sizes);
-int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t* sizes, const uint8_t* ins, uint32_t L);
+int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t* sizes, const uint8_t* ins, uint32_t L,
+                     const unsigned long long* pairs, size_t n_pairs);
 int pooldev_list_get(txv_ctx* c, PoolDev* s, std::vector<uint8_t>& keys, std::vector<uint32_t>& sizes,
-                     std::vector<uint8_t>& ins);
+                     std::vector<uint8_t>& ins, std::vector<unsigned long long>* pairs);
+void pooldev_senders_finish(PoolDev* s, int slot);
+void pooldev_senders_stats(const PoolDev* s, uint64_t out[4]);
+int pooldev_sent_by(txv_ctx* c, PoolDev* s, const uint8_t* h_keys, uint64_t id, uint32_t n, const uint16_t* peers,
+                    uint32_t n_peers, uint32_t* bits_out);
 void pooldev_result(const PoolDev* s, int slot, int64_t res[4]);
 constexpr int kPdRing = 8;   // = PoolDev::kPdRing (runtime.cpp)
 void pooldev_set_occupant(PoolDev* s, int slot, uint64_t id, uint32_t n_upd, uint32_t n, bool routed = false);
@@ -407,7 +414,58 @@ struct txv_pool {
   int next_slot = 0;
   uint32_t batch_hint = 0;                         // the largest CheckTx batch submitted to the device
   int64_t infl_len = 0, infl_bytes = 0;
+  // TXV_POOL_SENDERS: MempoolTxVote.Senders of the host list's entries (senders_dev.h).  An entry is
+  // named by the serial number its node got at push_back (txs_serial, by node index): KeyList hands
+  // a removed node's index out again, a serial never, so a recycled node cannot inherit a set.  A
+  // removed entry's words stay behind, unreachable, until sn_reserve rebuilds the set; the rebuild
+  // renumbers the live entries 0 .. len - 1 in list order (what a compaction does to positions).
+  bool senders_on = false;
+  std::vector<uint32_t> txs_serial;
+  uint32_t next_serial = 0;
+  std::vector<txv_senders::word_t> sn;             // the set's slots (a power of two)
+  uint64_t sn_words = 0;                           // words stored, dead entries' included
+  uint64_t sn_seed = 0;
+  uint32_t sn_rebuilds = 0;
   ~txv_pool();
+
+  // the set has room for `add` more words at no more than half load: else rebuilt without the
+  // dead entries' words, and if that is not enough, at twice the size (again, until it is)
+  void sn_reserve(uint64_t add, bool force = false) {
+    if (!force && (sn_words + add) * 2 <= sn.size()) return;
+    std::vector<uint32_t> npos(next_serial, txv_senders::kNone);
+    uint32_t r = 0;
+    for (int32_t e = txs.head; e >= 0; e = txs.nodes[e].next) {
+      npos[txs_serial[e]] = r;
+      txs_serial[e] = r++;
+    }
+    uint64_t live = 0;
+    for (txv_senders::word_t& w : sn) {
+      w = txv_senders::remap(w, npos.data(), next_serial);
+      live += w != 0;
+    }
+    size_t cap = sn.size();
+    while ((live + add) * 2 > cap) cap *= 2;
+    std::vector<txv_senders::word_t> old(cap, 0);
+    old.swap(sn);
+    for (txv_senders::word_t w : old)
+      if (w) (void)txv_senders::insert(sn.data(), sn.size() - 1, w, sn_seed);
+    next_serial = r;
+    sn_words = live;
+    ++sn_rebuilds;
+  }
+  // Senders.LoadOrStore(sender) of the entry in node e
+  void sn_add(int32_t e, uint16_t sender) {
+    sn_words += txv_senders::insert(sn.data(), sn.size() - 1, txv_senders::pair_word(txs_serial[e], sender), sn_seed) > 0;
+  }
+  // the set's first size: two senders per entry of a full pool, of at most 4096 entries (a larger
+  // pool's set grows with its content: a Flush or a move of the list to HBM costs the slots it
+  // clears, not the pool's configured Size)
+  size_t sn_initial() const { return (size_t)txv_senders::slots_for(2 * (uint64_t)std::min<uint32_t>(cfg.size, 4096)); }
+  void sn_clear() {
+    sn.assign(sn_initial(), 0);
+    sn_words = 0;
+    next_serial = 0;
+  }
 
   bool cache_push(const Key& k) {                  // mapTxCache.Push
     if (!cache_on) return true;
@@ -541,7 +599,8 @@ constexpr uint32_t kAdmitAhead = 16;
 
 uint64_t batch_tab_hash(const Key& k) { return key_hash(k, 0x9e3779b97f4a7c15ULL); }
 
-bool batch_check(txv_pool* p, txv_ctx* ctx, BatchScratch& S, const Key* keys, uint32_t n, uint8_t* status_out) {
+bool batch_check(txv_pool* p, txv_ctx* ctx, BatchScratch& S, const Key* keys, uint32_t n, uint8_t* status_out,
+                 const uint16_t* senders) {
   static const bool prof = getenv("TXV_PROFILE_HOST") != nullptr;
   std::chrono::steady_clock::time_point tp[16];
   int ntp = 0;
@@ -811,9 +870,16 @@ bool batch_check(txv_pool* p, txv_ctx* ctx, BatchScratch& S, const Key* keys, ui
     next_indices(p->txs, A, p->idx_t);
     p->txs.nodes.resize(std::max<size_t>(p->txs.nodes.size(), (size_t)p->idx_t[A - 1] + 1));
   }
+  const bool sn = p->senders_on;
+  const uint32_t serial0 = p->next_serial;                 // the admitted votes' entries: serial0 + rank
+  if (sn) {
+    if (p->txs_serial.size() < p->txs.nodes.size()) p->txs_serial.resize(p->txs.nodes.capacity());
+    p->next_serial += A;
+  }
   auto write_node = [&](uint32_t i, uint32_t a) {
     p->txs.nodes[p->idx_t[a]] = KeyList::Node{keys[i], sizes[i], a ? p->idx_t[a - 1] : old_tail,
                                               a + 1 < A ? p->idx_t[a + 1] : -1};
+    if (sn) p->txs_serial[p->idx_t[a]] = serial0 + a;
   };
   if (!may_cut) {
     pool_parallel_for(p, ctx, P, [&](uint32_t c0, uint32_t c1) {
@@ -971,18 +1037,38 @@ bool batch_check(txv_pool* p, txv_ctx* ctx, BatchScratch& S, const Key* keys, ui
   }
   mark();
   // 5. txsMap.Store of the admitted votes (batch order within each partition: a key admitted
-  //    twice keeps its later node, as the sequential Store does)
-  if (A) {
+  //    twice keeps its later node, as the sequential Store does).  With TXV_POOL_SENDERS the same
+  //    pass records the senders: a partition's votes are visited in arrival order and every vote of
+  //    one key is in one partition, so when vote i is reached the partition's index holds for its
+  //    key exactly what txsMap held when the sequential loop reached it -- the latest earlier
+  //    admission of the batch, else the entry from before the batch -- and an ErrTxInCache vote
+  //    adds its sender to that entry (:213-227).  The partitions' threads share the set: its
+  //    inserts are compare-and-swaps (senders_dev.h).
+  if (A || sn) {
+    std::atomic<uint64_t> stored{0};
     per_part([&](uint32_t q) {
       FlatIndex& f = *p->txs_map.p[q];
       const uint32_t lo = S.cnt[q], hi = S.cnt[q + 1];
+      uint64_t st = 0;
+      auto record = [&](int32_t e, uint32_t i) {
+        st += txv_senders::insert(p->sn.data(), p->sn.size() - 1,
+                                  txv_senders::pair_word(p->txs_serial[e], senders ? senders[i] : 0), p->sn_seed) > 0;
+      };
       for (uint32_t j = lo; j < hi; ++j) {
         if (j + 2 * kAdmitAhead < hi) __builtin_prefetch(&keys[S.order[j + 2 * kAdmitAhead]]);
         if (j + kAdmitAhead < hi) f.prefetch(keys[S.order[j + kAdmitAhead]]);
         const uint32_t i = S.order[j];
-        if (S.adm[i] >= 0) f.put(keys[i], p->idx_t[S.adm[i]]);
+        if (S.adm[i] >= 0) {
+          f.put(keys[i], p->idx_t[S.adm[i]]);
+          if (sn) record(p->idx_t[S.adm[i]], i);
+        } else if (sn && status_out[i] == TXV_POOL_ERR_IN_CACHE) {
+          const int32_t e = f.find(keys[i]);
+          if (e >= 0) record(e, i);
+        }
       }
+      if (st) stored.fetch_add(st, std::memory_order_relaxed);
     });
+    p->sn_words += stored.load();
     p->txs_bytes += (int64_t)admitted_bytes;
   }
   mark();
@@ -1024,6 +1110,11 @@ int txv_pool_new(const txv_pool_config* cfg, int64_t height, txv_pool** out) {
   if (p->cache_on) p->cache_map.reserve(std::min<uint32_t>(p->cfg.cache_size, 1u << 22));
   p->txs_map.reserve(std::min<uint32_t>(p->cfg.size, 1u << 22));
   p->txs.nodes.reserve(std::min<uint32_t>(p->cfg.size, 1u << 22));   // no reallocation while the pool fills
+  p->senders_on = (p->cfg.flags & TXV_POOL_SENDERS) != 0;
+  if (p->senders_on) {
+    p->sn.assign(p->sn_initial(), 0);
+    p->sn_seed = g_key_seed;
+  }
   *out = p;
   return TXV_OK;
 }
@@ -1043,20 +1134,25 @@ int list_to_host(txv_pool* p, txv_ctx* ctx);
 int drain_flights(txv_pool* p, bool flush = true);
 void publish_locked(txv_pool* p);
 
-int pool_admit_body(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out);
-int pool_admit(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out) {
-  const int r = pool_admit_body(p, ctx, keys, n, status_out);
+// senders (or null: every vote from UnknownPeerID 0): TxInfo.SenderID per vote, recorded by a pool
+// with TXV_POOL_SENDERS
+int pool_admit_body(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out, const uint16_t* senders);
+int pool_admit(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out,
+               const uint16_t* senders = nullptr) {
+  const int r = pool_admit_body(p, ctx, keys, n, status_out, senders);
   publish_locked(p);
   return r;
 }
-int pool_admit_body(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out) {
+int pool_admit_body(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint8_t* status_out, const uint16_t* senders) {
   if (int r = drain_flights(p)) return r;
   if (int r = list_to_host(p, ctx)) return r;
   if (int r = cache_to_host(p, ctx)) return r;
   host_cache_written(p);
   const auto t1 = std::chrono::steady_clock::now();
   const int64_t max_tx = (int64_t)p->cfg.max_msg_bytes - 8;   // calcMaxTxSize
-  if (n >= 4096 && batch_check(p, ctx, p->bs, keys, n, status_out)) {
+  const bool sn = p->senders_on;
+  if (sn) p->sn_reserve(n);                                   // (a vote stores at most one word)
+  if (n >= 4096 && batch_check(p, ctx, p->bs, keys, n, status_out, senders)) {
     if (getenv("TXV_PROFILE_HOST")) {
       const auto t2 = std::chrono::steady_clock::now();
       fprintf(stderr, "[txv pool] batch-check=%.3fms n=%u\n", std::chrono::duration<double, std::milli>(t2 - t1).count(), n);
@@ -1082,9 +1178,22 @@ int pool_admit_body(txv_pool* p, txv_ctx* ctx, const Key* keys, uint32_t n, uint
       continue;
     }
     if ((int64_t)sz > max_tx) { status_out[i] = TXV_POOL_ERR_TOO_LARGE; continue; }
-    if (!p->cache_push(keys[i])) { status_out[i] = TXV_POOL_ERR_IN_CACHE; continue; }
+    if (!p->cache_push(keys[i])) {
+      status_out[i] = TXV_POOL_ERR_IN_CACHE;
+      if (sn) {   // :213-227: the key still in txsMap -> its entry's Senders.LoadOrStore
+        const int32_t e = p->txs_map.find(keys[i]);
+        if (e >= 0) p->sn_add(e, senders ? senders[i] : 0);
+      }
+      continue;
+    }
     if (!sz && (p->cfg.flags & TXV_POOL_WAL)) { status_out[i] = TXV_POOL_ERR_ENCODING; continue; }
-    p->txs_map.put(keys[i], p->txs.push_back(keys[i], sz));     // addTx (txsMap.Store overwrites)
+    const int32_t node = p->txs.push_back(keys[i], sz);
+    p->txs_map.put(keys[i], node);                              // addTx (txsMap.Store overwrites)
+    if (sn) {                                                   // :250: Senders = {the admitting peer}
+      if (p->txs_serial.size() < p->txs.nodes.size()) p->txs_serial.resize(p->txs.nodes.capacity());
+      p->txs_serial[node] = p->next_serial++;
+      p->sn_add(node, senders ? senders[i] : 0);
+    }
     p->txs_bytes += sz;
     status_out[i] = TXV_POOL_OK;
   }
@@ -1147,7 +1256,7 @@ int cache_to_dev(txv_pool* p, txv_ctx* ctx, uint32_t n) {
     p->dev = nullptr;
   }
   PoolDev* before = p->dev;
-  if (int r = pooldev_bind(ctx, &p->dev, p->cache_on ? p->cfg.cache_size : 0u, n)) return r;
+  if (int r = pooldev_bind(ctx, &p->dev, p->cache_on ? p->cfg.cache_size : 0u, n, p->senders_on)) return r;
   if (p->dev != before) p->dev_state = txv_pool::kHostAhead;   // a new device copy starts empty
   if (p->dev_state != txv_pool::kHostAhead) return TXV_OK;
   std::vector<Key> kl;
@@ -1163,7 +1272,8 @@ int list_to_host(txv_pool* p, txv_ctx* ctx) {
   if (!p->list_dev) return TXV_OK;
   std::vector<uint8_t> kb, ins;
   std::vector<uint32_t> sz;
-  if (int r = pooldev_list_get(ctx, p->dev, kb, sz, ins)) return r;
+  std::vector<unsigned long long> pairs;
+  if (int r = pooldev_list_get(ctx, p->dev, kb, sz, ins, p->senders_on ? &pairs : nullptr)) return r;
   const uint32_t L = (uint32_t)sz.size();
   const Key* keys = reinterpret_cast<const Key*>(kb.data());
   KeyList& T = p->txs;
@@ -1181,6 +1291,14 @@ int list_to_host(txv_pool* p, txv_ctx* ctx) {
         if (ins[e] && PartIndex::part(keys[e]) == q) f.put(keys[e], (int32_t)e);
     }
   }, 1);
+  if (p->senders_on) {   // the entries' Senders came with them, named by rank: the nodes' serials
+    p->txs_serial.resize(std::max<size_t>(T.nodes.capacity(), L));
+    for (uint32_t e = 0; e < L; ++e) p->txs_serial[e] = e;
+    p->sn_clear();
+    p->next_serial = L;
+    if (pairs.size() * 2 > p->sn.size()) p->sn.assign(txv_senders::slots_for(pairs.size()), 0);   // (cleared just above)
+    for (unsigned long long w : pairs) p->sn_words += txv_senders::insert(p->sn.data(), p->sn.size() - 1, w, p->sn_seed) > 0;
+  }
   p->list_dev = false;
   return TXV_OK;
 }
@@ -1199,8 +1317,14 @@ int list_to_dev(txv_pool* p, txv_ctx* ctx) {
     sz.push_back(T.nodes[e].size);
     ins.push_back(p->txs_map.find(T.nodes[e].k) == e);
   }
+  std::vector<unsigned long long> pairs;
+  if (p->senders_on) {   // the live entries' Senders go along, named by rank (the rebuild renumbers so)
+    p->sn_reserve(0, true);
+    for (txv_senders::word_t w : p->sn)
+      if (w) pairs.push_back(w);
+  }
   if (int r = pooldev_list_put(ctx, p->dev, reinterpret_cast<const uint8_t*>(kl.data()), sz.data(), ins.data(),
-                               (uint32_t)kl.size()))
+                               (uint32_t)kl.size(), pairs.data(), pairs.size()))
     return r;
   p->list_dev = true;
   return TXV_OK;
@@ -1324,6 +1448,7 @@ uint64_t live_ub(const txv_pool* p) { return (uint64_t)p->txs.len + (uint64_t)st
 void list_counts(txv_pool* p, int slot) {
   int64_t res[4];
   pooldev_result(p->dev, slot, res);
+  if (p->senders_on) pooldev_senders_finish(p->dev, slot);
   p->txs.len = (size_t)((int64_t)p->txs.len + res[0] - res[2]);
   p->txs_bytes += res[1] - res[3];
   publish(p);
@@ -1441,19 +1566,22 @@ int txv_pool_check_dev(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const 
 // made to wait for them -- the ingest's TxFlow chain reads them without a host round trip.
 static int check_dev_submit_locked(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                                    const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
-                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done);
+                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done,
+                                   const uint16_t* senders = nullptr);
 int txv_pool_check_dev_submit(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                               const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
-                              uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done) {
+                              uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done,
+                              const uint16_t* senders) {
   std::lock_guard<std::mutex> g(p->mu);
   return check_dev_submit_locked(p, ctx, d_keys, d_sizes, d_valid, valid_ok, n, bytes_bound, after, d_status_copy,
-                                 then_stream, ticket, done);
+                                 then_stream, ticket, done, senders);
 }
 
 // (p->mu held; the new ticket is p->tickets.back() when *done)
 static int check_dev_submit_locked(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                                    const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
-                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done) {
+                                   uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done,
+                                   const uint16_t* senders) {
   *done = false;
   *ticket = 0;
   if (!dev_mode(p) || !n) return TXV_OK;
@@ -1471,7 +1599,7 @@ static int check_dev_submit_locked(txv_pool* p, txv_ctx* ctx, const uint32_t* d_
   p->pend_slot = -1;
   if ((r = pooldev_enqueue(ctx, p->dev, slot, nullptr, nullptr, nullptr, d_keys, d_sizes, d_valid, valid_ok, n, max_tx,
                            (p->cfg.flags & TXV_POOL_WAL) != 0, false, after, true, live_ub(p), n_upd, d_status_copy,
-                           then_stream)))
+                           then_stream, senders)))
     return r;
   if (p->cache_on) p->dev_state = txv_pool::kDevAhead;
   p->next_slot = (slot + 1) % kPdRing;
@@ -1497,14 +1625,17 @@ uint32_t txv_pool_max_msg_bytes(txv_pool* p) {
   return p->cfg.max_msg_bytes;
 }
 
-extern "C" {
+// a sender column is taken only by a pool that keeps Senders
+static bool senders_arg_ok(const txv_pool* p, const uint16_t* senders) { return !senders || p->senders_on; }
+bool txv_pool_keeps_senders(const txv_pool* p) { return p->senders_on; }   // (runtime.cpp's ingest)
 
 // CheckTxWithInfo for n votes whose keys (n x 32 bytes) and Size() values are known (computed on
 // the device from decoded wire records by txv_ingest_msgs, or by the caller); ctx may be NULL
 // (the batch passes then run on the pool's own worker threads)
-int txv_pool_check_keys(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const uint32_t* sizes, uint32_t n,
-                        uint8_t* status_out) {
+static int check_keys_from(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const uint32_t* sizes, uint32_t n,
+                           const uint16_t* senders, uint8_t* status_out) {
   if (!p || (n && (!keys32 || !sizes || !status_out))) return TXV_EINVAL;
+  if (!senders_arg_ok(p, senders)) return TXV_ESTATE;
   std::lock_guard<std::mutex> g(p->mu);
   if (dev_mode(p) && ctx && n) {   // the device path: keys and sizes uploaded, decided on the GPU
     const int64_t max_tx = (int64_t)p->cfg.max_msg_bytes - 8;
@@ -1516,7 +1647,7 @@ int txv_pool_check_keys(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const 
       if ((r = sync_batch_begin(p, ctx, n, &slot, &n_upd))) return r;
       if ((r = pooldev_check(ctx, p->dev, nullptr, keys32, sizes, nullptr, nullptr, nullptr, 0, n, max_tx,
                              (p->cfg.flags & TXV_POOL_WAL) != 0, nullptr, status_out, nullptr, true, live_ub(p), slot,
-                             n_upd)))
+                             n_upd, senders)))
         return r;
       if (p->cache_on) p->dev_state = txv_pool::kDevAhead;
       list_counts(p, slot);
@@ -1524,18 +1655,33 @@ int txv_pool_check_keys(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const 
     }
   }
   p->sizes.assign(sizes, sizes + n);
-  return pool_admit(p, ctx, reinterpret_cast<const Key*>(keys32), n, status_out);
+  return pool_admit(p, ctx, reinterpret_cast<const Key*>(keys32), n, status_out, senders);
 }
+
+extern "C" {
+
+int txv_pool_check_keys(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const uint32_t* sizes, uint32_t n,
+                        uint8_t* status_out) {
+  return check_keys_from(p, ctx, keys32, sizes, n, nullptr, status_out);
+}
+// CheckTxWithInfo: txv_pool_check_keys with TxInfo.SenderID per vote (include/txvote.h)
+int txv_pool_check_keys_from(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, const uint32_t* sizes, uint32_t n,
+                             const uint16_t* senders, uint8_t* status_out) {
+  return check_keys_from(p, ctx, keys32, sizes, n, senders, status_out);
+}
+
+}  // extern "C"
 
 // CheckTxWithInfo for a batch, submitted: with TXV_POOL_DEVICE_CACHE (and no long signature,
 // caps that cannot bind, a free flight slot) the keys, decisions and new cache are enqueued on
 // the engine's stream and the call returns; otherwise the batch is checked on the host here (any
 // device batches still in flight are finished first).  Either way the batch is CheckTx'd in
 // submission order, and txv_pool_check_wait returns its statuses.
-int txv_pool_check_submit(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
-                          const uint64_t* sig_full_off, uint64_t* ticket) {
+static int check_submit_from(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
+                             const uint64_t* sig_full_off, const uint16_t* senders, uint64_t* ticket) {
   if (!p || !ctx || !v || !ticket) return TXV_EINVAL;
   *ticket = 0;
+  if (!senders_arg_ok(p, senders)) return TXV_ESTATE;
   const auto t0 = std::chrono::steady_clock::now();
   // the device path: Size() on the host workers (with the pushes, the bytes and any long
   // signature) before the pool's lock is taken (cfg is fixed at txv_pool_new), then keys,
@@ -1585,7 +1731,8 @@ int txv_pool_check_submit(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const u
       p->pend_n = 0;
       p->pend_slot = -1;
       if ((r = pooldev_enqueue(ctx, p->dev, slot, v, nullptr, dsz.data(), nullptr, nullptr, nullptr, 0, v->n, max_tx,
-                               (p->cfg.flags & TXV_POOL_WAL) != 0, false, nullptr, true, live_ub(p), n_upd)))
+                               (p->cfg.flags & TXV_POOL_WAL) != 0, false, nullptr, true, live_ub(p), n_upd, nullptr,
+                               nullptr, senders)))
         return r;
       t.n_upd = n_upd;
       pooldev_set_occupant(p->dev, slot, t.id, n_upd, v->n);   // txv_submit_checked may read it from HBM
@@ -1614,11 +1761,22 @@ int txv_pool_check_submit(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const u
     fprintf(stderr, "[txv pool] keys+sizes=%.3fms n=%u\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), v->n);
   t.st.resize(v->n);
-  if ((r = pool_admit(p, ctx, keys, v->n, t.st.data()))) return r;
+  if ((r = pool_admit(p, ctx, keys, v->n, t.st.data(), senders))) return r;
   t.done = true;
   p->tickets.push_back(std::move(t));
   *ticket = p->next_ticket++;
   return TXV_OK;
+}
+
+extern "C" {
+
+int txv_pool_check_submit(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
+                          const uint64_t* sig_full_off, uint64_t* ticket) {
+  return check_submit_from(p, ctx, v, sig_full, sig_full_off, nullptr, ticket);
+}
+int txv_pool_check_submit_from(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
+                               const uint64_t* sig_full_off, const uint16_t* senders, uint64_t* ticket) {
+  return check_submit_from(p, ctx, v, sig_full, sig_full_off, senders, ticket);
 }
 
 // TryAddVote for the batch a CheckTx ticket is deciding (include/txvote.h): while the batch is in
@@ -1919,13 +2077,17 @@ int txv_pool_check_wait(txv_pool* p, uint64_t ticket, uint8_t* status_out) {
   return TXV_ESTATE;
 }
 
-int txv_pool_check(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
-                   const uint64_t* sig_full_off, uint8_t* status_out) {
+int txv_pool_check_from(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
+                        const uint64_t* sig_full_off, const uint16_t* senders, uint8_t* status_out) {
   if (!p || !ctx || !v || (v->n && !status_out)) return TXV_EINVAL;
   uint64_t t = 0;
-  int r = txv_pool_check_submit(p, ctx, v, sig_full, sig_full_off, &t);
+  int r = check_submit_from(p, ctx, v, sig_full, sig_full_off, senders, &t);
   if (r) return r;
   return txv_pool_check_wait(p, t, status_out);
+}
+int txv_pool_check(txv_pool* p, txv_ctx* ctx, const txv_votes* v, const uint8_t* sig_full,
+                   const uint64_t* sig_full_off, uint8_t* status_out) {
+  return txv_pool_check_from(p, ctx, v, sig_full, sig_full_off, nullptr, status_out);
 }
 
 // the order-independent half of CheckTxWithInfo for a batch (txvotepool.go:187-261): every vote's
@@ -2098,7 +2260,15 @@ int txv_pool_reap(txv_pool* p, int64_t max, uint8_t* keys_out, uint32_t* sizes_o
 
 int txv_pool_receive(txv_pool* p, txv_ctx* ctx, const uint8_t* wire, uint64_t wire_bytes, const uint64_t* msg_off,
                      const uint32_t* msg_len, uint32_t n, uint8_t* wire_status, uint8_t* pool_status) {
+  return txv_pool_receive_from(p, ctx, wire, wire_bytes, msg_off, msg_len, n, nullptr, wire_status, pool_status);
+}
+
+// Reactor.Receive with src's peer id per message (reactor.go:183-188: txInfo.SenderID = GetID(src))
+int txv_pool_receive_from(txv_pool* p, txv_ctx* ctx, const uint8_t* wire, uint64_t wire_bytes, const uint64_t* msg_off,
+                          const uint32_t* msg_len, uint32_t n, const uint16_t* senders, uint8_t* wire_status,
+                          uint8_t* pool_status) {
   if (!p || !ctx || (n && (!wire_status || !pool_status))) return TXV_EINVAL;
+  if (!senders_arg_ok(p, senders)) return TXV_ESTATE;
   // decodeMsg for the batch (GPU), then the decoded TxVoteMessages in arrival order
   std::vector<int64_t> height(n), ts_sec(n);
   std::vector<int32_t> ts_nanos(n);
@@ -2138,7 +2308,12 @@ int txv_pool_receive(txv_pool* p, txv_ctx* ctx, const uint8_t* wire, uint64_t wi
   v.ts_sec = ts_sec.data(); v.ts_nanos = ts_nanos.data(); v.addr = addr.data(); v.addr_len = addr_len.data();
   v.sig = sig.data(); v.sig_len = sig_len.data();
   std::vector<uint8_t> st(v.n);
-  r = txv_pool_check(p, ctx, &v, wire, sig_off.data(), st.data());
+  std::vector<uint16_t> snd;                     // the decoded messages' senders, compacted alike
+  if (senders) {
+    snd.resize(ok.size());
+    for (size_t j = 0; j < ok.size(); ++j) snd[j] = senders[ok[j]];
+  }
+  r = txv_pool_check_from(p, ctx, &v, wire, sig_off.data(), senders ? snd.data() : nullptr, st.data());
   if (r) return r;
   for (size_t j = 0; j < ok.size(); ++j) pool_status[ok[j]] = st[j];
   return TXV_OK;
@@ -2191,9 +2366,74 @@ int txv_pool_flush(txv_pool* p) {
   p->cache.clear(); p->cache_map.clear();
   host_cache_written(p);
   p->txs.clear(); p->txs_map.clear();
+  if (p->senders_on) p->sn_clear();                        // the entries' Senders go with them
   p->list_dev = false;                                     // the device's copy is dropped (re-sent empty)
   p->txs_bytes = 0;
   publish_locked(p);
+  return TXV_OK;
+}
+
+// broadcastTxRoutine's one question (reactor.go:245): has peer p already sent us vote i.  Row i of
+// bits_out ([n][ceil(n_peers / 32)] words): bit p set iff txsMap holds key i now and peers[p] is in
+// that entry's Senders (include/txvote.h).  Every submitted batch and Update is finished first.
+int txv_pool_sent_by(txv_pool* p, txv_ctx* ctx, const uint8_t* keys32, uint32_t n, const uint16_t* peers,
+                     uint32_t n_peers, uint32_t* bits_out) {
+  if (!p || !peers || !n_peers || (n && (!keys32 || !bits_out))) return TXV_EINVAL;
+  if (!p->senders_on) return TXV_ESTATE;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (int r = drain_flights(p)) return r;
+  // the list in HBM on ctx's device: looked up there (one wave per key); else it comes home first
+  if (p->list_dev && ctx && pooldev_same_device(ctx, p->dev)) return n ? pooldev_sent_by(ctx, p->dev, keys32, 0, n, peers, n_peers, bits_out) : TXV_OK;
+  if (int r = list_to_host(p, ctx)) return r;
+  const uint32_t W = (n_peers + 31) / 32;
+  const Key* keys = reinterpret_cast<const Key*>(keys32);
+  memset(bits_out, 0, (size_t)n * W * 4);
+  pool_parallel_for(p, ctx, n, [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t i = lo; i < hi; ++i) {
+      const int32_t e = p->txs_map.find(keys[i]);
+      if (e < 0) continue;
+      for (uint32_t q = 0; q < n_peers; ++q)
+        if (txv_senders::contains(p->sn.data(), p->sn.size() - 1, txv_senders::pair_word(p->txs_serial[e], peers[q]),
+                                  p->sn_seed))
+          bits_out[(size_t)i * W + q / 32] |= 1u << (q % 32);
+    }
+  }, 4096);
+  return TXV_OK;
+}
+
+// The same rows for the votes of a CheckTx ticket, looked up where the batch lies in the engine's
+// flight slot.  A ticket decided on the host holds no slot: TXV_ESTATE, the caller uses the key form.
+int txv_pool_ticket_sent_by(txv_pool* p, txv_ctx* ctx, uint64_t pool_ticket, const uint16_t* peers, uint32_t n_peers,
+                            uint32_t* bits_out) {
+  if (!p || !ctx || !pool_ticket || !peers || !n_peers || !bits_out) return TXV_EINVAL;
+  if (!p->senders_on) return TXV_ESTATE;
+  std::lock_guard<std::mutex> g(p->mu);
+  auto it = std::find_if(p->tickets.begin(), p->tickets.end(), [&](const txv_pool::Ticket& t) { return t.id == pool_ticket; });
+  if (it != p->tickets.end() && (it->upd || it->slot < 0)) return TXV_ESTATE;   // decided on the host
+  if (!p->list_dev || !p->dev || !pooldev_same_device(ctx, p->dev) || !pooldev_holds(p->dev, pool_ticket)) return TXV_ESTATE;
+  if (int r = drain_flights(p)) return r;      // the ticket, and every batch that reads or writes the sets
+  if (!p->list_dev || !pooldev_holds(p->dev, pool_ticket)) return TXV_ESTATE;
+  const int r = pooldev_sent_by(ctx, p->dev, nullptr, pool_ticket, 0, peers, n_peers, bits_out);
+  return r == 1 ? TXV_ESTATE : r;
+}
+
+// test hook: stats_out = {words stored (dead entries' included; in HBM an upper bound), slots,
+// rebuilds of the set so far, compactions of the list in HBM so far, 1 when the list and its sets
+// are in HBM now}
+int txv_pool_senders_stats(txv_pool* p, uint64_t stats_out[5]) {
+  if (!p || !stats_out) return TXV_EINVAL;
+  if (!p->senders_on) return TXV_ESTATE;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->list_dev) {                      // the engine's set: {bound of the words, slots, rebuilds, list compactions}
+    pooldev_senders_stats(p->dev, stats_out);
+    stats_out[4] = 1;
+    return TXV_OK;
+  }
+  stats_out[4] = 0;
+  stats_out[0] = p->sn_words;
+  stats_out[1] = p->sn.size();
+  stats_out[2] = p->sn_rebuilds;
+  stats_out[3] = 0;
   return TXV_OK;
 }
 

@@ -16,6 +16,9 @@
 // kListTomb a removed entry).  A list position is never reused before a compaction, so the list
 // order is the reference's clist order: appends at the tail, removals leave a dead entry behind.
 constexpr uint32_t kListTomb = 0xFFFFFFFFu;
+// the index's home slot = txv_hash::key32(key, seed ^ kSeedList); the slot's tag = key word 3
+// (kernels_pool.hip list_home / list_insert; kernels_senders.hip probes the same index)
+constexpr uint64_t kSeedList = 0x13198A2E03707344ull;
 struct PoolListArgs {
   uint32_t* lk;               // [cap][8] entry keys
   uint32_t* lsz;              // [cap] entry Size()

@@ -429,6 +429,7 @@ struct txv_ctx {
     uint64_t wire_bytes = 0;       // bounds the decoded votes' summed TxVote.Size()
     int flow_err = 0;              // the admitted votes' AddVote chain could not be enqueued
     std::string flow_msg;
+    std::vector<uint16_t> senders; // txv_ingest_decode_from: the messages' peer ids (empty: all 0)
   } ing[kIngestRing];
   std::mutex sub_mu;               // txv_submit_votes / txv_submit_checked one at a time (the latter stages,
                                    // takes the pool's lock, then runs: no other submit in between)
@@ -4044,9 +4045,11 @@ int txv_decode_msgs(txv_ctx* c, const uint8_t* wire, uint64_t wire_bytes, const 
 }  // extern "C"
 
 uint32_t txv_pool_max_msg_bytes(txv_pool* p);  // pool.cpp
+bool txv_pool_keeps_senders(const txv_pool* p);   // pool.cpp
 int txv_pool_check_dev_submit(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                               const uint8_t* d_valid, uint8_t valid_ok, uint32_t n, uint64_t bytes_bound, void* after,
-                              uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done);   // pool.cpp
+                              uint8_t* d_status_copy, void* then_stream, uint64_t* ticket, bool* done,
+                              const uint16_t* senders = nullptr);   // pool.cpp
 int txv_pool_check_dev(txv_pool* p, txv_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_sizes,
                        const uint8_t* d_valid, const uint8_t* h_keys, const uint32_t* h_sizes, uint8_t valid_ok,
                        uint32_t n, uint64_t bytes_bound, void* after, uint8_t* status_out, bool* done);   // pool.cpp
@@ -4097,7 +4100,7 @@ int ingest_alloc(txv_ctx* c, txv_ctx::Ingest& g, Slot& s, uint64_t wire_bytes, u
 }
 
 int ingest_decode(txv_ctx* c, txv_pool* p, const uint8_t* wire, uint64_t wire_bytes, const uint64_t* msg_off,
-                  const uint32_t* msg_len, uint32_t n, uint64_t* ticket) {
+                  const uint32_t* msg_len, uint32_t n, uint64_t* ticket, const uint16_t* senders = nullptr) {
   if (wire_bytes >= (1ull << 32)) { c->err = "wire buffer >= 4 GiB"; return TXV_EINVAL; }
   uint32_t max_len = 0;
   for (uint32_t i = 0; i < n; ++i) {   // every message inside the buffer: the kernels trust these
@@ -4135,6 +4138,7 @@ int ingest_decode(txv_ctx* c, txv_pool* p, const uint8_t* wire, uint64_t wire_by
   if ((r = ingest_alloc(c, g, s, wire_bytes, n))) return r;
   g.n = n; g.n_adm = 0; g.flow_err = 0; g.flow_msg.clear(); g.pool = p; g.wire_bytes = wire_bytes;
   g.max_len = max_len; g.early = false;
+  if (senders) g.senders.assign(senders, senders + n); else g.senders.clear();
   const uint32_t n_chunks = (n + TXV_WIRE_BLOCK - 1) / TXV_WIRE_BLOCK;
   if (n) {
     if (!wire_reg) {
@@ -4321,7 +4325,8 @@ int ingest_admit_submit(txv_ctx* c, uint64_t t, uint8_t* wire_status, uint8_t* p
     const bool early = g.max_len <= kEarlyMaxLen;
     const int rd = txv_pool_check_dev_submit(g.pool, c, g.d_keys, g.d_sizes, g.d_status, TXV_WIRE_OK, n, g.wire_bytes,
                                              (void*)g.kev, early ? g.d_pstat : nullptr,
-                                             early ? (void*)c->key_stream : nullptr, &pt, &dev);
+                                             early ? (void*)c->key_stream : nullptr, &pt, &dev,
+                                             g.senders.empty() ? nullptr : g.senders.data());
     if (rd) {   // the pool is unchanged: the ticket ends here (no wait)
       (void)hipEventSynchronize(g.kev);
       std::lock_guard<std::mutex> lk(c->mu);
@@ -4372,8 +4377,10 @@ int ingest_admit_submit(txv_ctx* c, uint64_t t, uint8_t* wire_status, uint8_t* p
     std::vector<uint32_t> ok;
     std::vector<uint8_t> keys_c;
     std::vector<uint32_t> sizes_c;
+    std::vector<uint16_t> snd_c;
     const uint8_t* keys = reinterpret_cast<const uint8_t*>(g.h_keys);
     const uint32_t* sizes = g.h_sizes;
+    const uint16_t* snd = g.senders.empty() ? nullptr : g.senders.data();
     uint32_t m = n;
     if (!all_ok) {
       ok.reserve(n);
@@ -4390,9 +4397,14 @@ int ingest_admit_submit(txv_ctx* c, uint64_t t, uint8_t* wire_status, uint8_t* p
       }, 8192);
       keys = keys_c.data();
       sizes = sizes_c.data();
+      if (snd) {
+        snd_c.resize(std::max<uint32_t>(m, 1));
+        for (uint32_t q = 0; q < m; ++q) snd_c[q] = g.senders[ok[q]];
+        snd = snd_c.data();
+      }
     }
     std::unique_ptr<uint8_t[]> pst(new uint8_t[std::max<uint32_t>(m, 1)]);
-    int r = txv_pool_check_keys(g.pool, c, keys, sizes, m, pst.get());
+    int r = txv_pool_check_keys_from(g.pool, c, keys, sizes, m, snd, pst.get());
     if (r) {   // the pool is unchanged: the ticket ends here (no wait)
       std::lock_guard<std::mutex> lk(c->mu);
       ingest_drop(c, g, t);
@@ -4561,6 +4573,14 @@ int txv_ingest_decode(txv_ctx* c, txv_pool* p, const uint8_t* wire, uint64_t wir
   return ingest_decode(c, p, wire, wire_bytes, msg_off, msg_len, n, ticket);
 }
 
+int txv_ingest_decode_from(txv_ctx* c, txv_pool* p, const uint8_t* wire, uint64_t wire_bytes, const uint64_t* msg_off,
+                           const uint32_t* msg_len, uint32_t n, const uint16_t* senders, uint64_t* ticket) {
+  if (!c || !p || !ticket || (n && (!wire || !msg_off || !msg_len))) return TXV_EINVAL;
+  *ticket = 0;
+  if (senders && !txv_pool_keeps_senders(p)) return TXV_ESTATE;
+  return ingest_decode(c, p, wire, wire_bytes, msg_off, msg_len, n, ticket, senders);
+}
+
 int txv_ingest_admit(txv_ctx* c, uint64_t ticket, uint8_t* wire_status, uint8_t* pool_status) {
   if (!c) return TXV_EINVAL;
   return ingest_admit(c, ticket, wire_status, pool_status);
@@ -4613,8 +4633,17 @@ int txv_ingest_msgs(txv_ctx* c, txv_pool* p, const uint8_t* wire, uint64_t wire_
 // the pool (freed by pooldev_free, whatever became of the context), on the device of the context
 // first used; the work runs on that context's key stream.
 #include "pool_dev.h"
+#include "senders_dev.h"
 extern "C" size_t txv_pooldev_tmp_bytes(uint32_t n, uint32_t C);
-extern "C" hipError_t txv_pooldev_run(const PoolDevArgs* a, hipStream_t st);
+extern "C" hipError_t txv_pooldev_run(const PoolDevArgs* a, const SendersArgs* sn, hipStream_t st);
+extern "C" size_t txv_senders_tmp_bytes(uint32_t n);
+extern "C" hipError_t txv_senders_rebuild(const txv_senders::word_t* old, uint64_t n_old, const uint8_t* alive,
+                                          const uint32_t* npos, txv_senders::word_t* neu, uint64_t n_new, uint64_t seed,
+                                          unsigned long long* count, hipStream_t st);
+extern "C" hipError_t txv_senders_query(const uint32_t* keys, const uint8_t* status, uint32_t n, const uint16_t* peers,
+                                        uint32_t n_peers, const uint32_t* lk, const unsigned long long* li, uint32_t imask,
+                                        const txv_senders::word_t* slots, uint64_t mask, uint64_t seed, uint32_t* bits,
+                                        hipStream_t st);
 extern "C" hipError_t txv_pooldev_index(const uint32_t* ck, uint32_t L, uint32_t* ci, uint32_t icap, uint64_t seed,
                                         hipStream_t st);
 extern "C" size_t txv_poollist_tmp_bytes(uint32_t cap);
@@ -4663,6 +4692,19 @@ struct PoolDev {
   size_t ltmp_bytes = 0;
   uint64_t tail_ub = 0;                    // host: an upper bound of the tail (the appends enqueued)
   uint64_t list_hint = 0;                  // entries the list is expected to hold (the pool's Size cap, clamped)
+  // TXV_POOL_SENDERS (senders_dev.h): the entries' Senders, one set of (position, sender) words
+  // beside the list, in two buffers (a rebuild fills the other one); its word count on the device,
+  // and the host's upper bound of it: one more per recorded vote of every batch enqueued, lowered
+  // to the exact count (Flight::h_sn) as batches finish
+  bool sn_on = false;
+  txv_senders::word_t* sn[2] = {nullptr, nullptr};
+  uint64_t sn_cap[2] = {0, 0};
+  int sn_cur = 0;
+  unsigned long long* sn_count = nullptr;
+  unsigned long long* h_sn_count = nullptr;       // pinned: a rebuild's count, an upload's staging
+  uint32_t *sn_okf = nullptr, *sn_cpos = nullptr, *sn_ckey = nullptr, *sn_cidx = nullptr;   // [cap_n] scratch
+  uint64_t sn_bound = 0, sn_enq = 0;               // the bound; recorded votes enqueued so far
+  uint32_t sn_rebuilds = 0, l_compactions = 0;
   // per batch in flight (kPdRing): its inputs, statuses and keys, and the event that ends it
   static constexpr int kPdRing = 8;
   struct Flight {
@@ -4671,6 +4713,9 @@ struct PoolDev {
     uint32_t *h_sig = nullptr, *h_len = nullptr, *h_keys = nullptr, *h_sizes = nullptr;
     uint8_t *h_status = nullptr, *m_status = nullptr;   // mapped: pd_status writes the batch's statuses here
     uint64_t *h_res = nullptr, *m_res = nullptr;        // mapped, per tile (entries, bytes): [2 ntm] appended, [2 ntm] removed
+    uint16_t *d_snd = nullptr, *h_snd = nullptr;        // TXV_POOL_SENDERS: the batch's sender column
+    unsigned long long* h_sn = nullptr;                 // ... the set's word count after the batch (pinned)
+    uint64_t sn_mark = 0;                               // ... sn_enq at its enqueue (0: it recorded nothing)
     uint32_t nt_app = 0, nt_rm = 0;                // tiles of the batch in flight with partials there
     hipEvent_t ev = nullptr;
     hipEvent_t up_ev = nullptr;                    // the slot's signature uploads done (copy stream)
@@ -4703,10 +4748,12 @@ struct PoolDev {
     dfree(detached); dfree(pst); dfree(pend); dfree(xs); dfree(xn); dfree(tiles); dfree(tk); dfree(okpos);
     for (ListBuf& b : lb) { dfree(b.k); dfree(b.sz); dfree(b.fl); dfree(b.ix); }
     dfree(ltail); dfree(lnpos); dfree(d_err); hfree(h_err);
+    dfree(sn[0]); dfree(sn[1]); dfree(sn_count); hfree(h_sn_count); dfree(sn_okf); dfree(sn_cpos); dfree(sn_ckey); dfree(sn_cidx);
     if (ltmp) (void)hipFree(ltmp);
     for (Flight& f : fl) {
       dfree(f.d_sig); dfree(f.d_len); dfree(f.d_keys); dfree(f.d_sizes); dfree(f.d_status);
       hfree(f.h_sig); hfree(f.h_len); hfree(f.h_keys); hfree(f.h_sizes); hfree(f.h_status); hfree(f.h_res);
+      dfree(f.d_snd); hfree(f.h_snd); hfree(f.h_sn);
       if (f.ev) (void)hipEventDestroy(f.ev);
       if (f.up_ev) (void)hipEventDestroy(f.up_ev);
       if (f.cons_ev) (void)hipEventDestroy(f.cons_ev);
@@ -4733,7 +4780,7 @@ size_t pooldev_tile_words(uint32_t m, uint32_t C) {
 
 // (re)binds the engine to c's device with capacity C and room for n-vote batches; a new cache
 // starts empty (length 0)
-int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n) {
+int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n, bool senders) {
   HIP_TRY(c, hipSetDevice(c->device));
   PoolDev* s = *sp;
   if (s && (s->device != c->device || s->C != C)) { delete s; s = *sp = nullptr; }
@@ -4744,6 +4791,7 @@ int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n) {
     *sp = s;
     s->device = c->device;
     s->C = C;
+    s->sn_on = senders;
     s->seed = ((uint64_t)std::random_device{}() << 32 | std::random_device{}()) ^ 0x706f6f6c6b657973ULL;
     s->icap = 16;
     while (s->icap < 2 * std::max<uint32_t>(C, 1)) s->icap *= 2;
@@ -4757,6 +4805,12 @@ int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n) {
       return r;
     HIP_TRY(c, hipMemset(s->d_err, 0, 4));
     *s->h_err = 0;
+    if (senders) {
+      if ((r = dalloc(c, &s->sn_count, 1)) || (r = halloc(c, &s->h_sn_count, 1))) return r;
+      HIP_TRY(c, hipMemset(s->sn_count, 0, 8));
+      for (PoolDev::Flight& f : s->fl)
+        if ((r = halloc(c, &f.h_sn, 1))) return r;
+    }
     HIP_TRY(c, hipMemset(s->tk, 0, 16));
     HIP_TRY(c, hipMemset(s->ltail, 0, 8));
     HIP_TRY(c, hipMemset(s->ci[0], 0, (size_t)s->icap * 4));
@@ -4805,8 +4859,15 @@ int pooldev_bind(txv_ctx* c, PoolDev** sp, uint32_t C, uint32_t n) {
           (r = halloc(c, &f.h_len, m)) || (r = halloc(c, &f.h_keys, (size_t)m * 8)) || (r = halloc(c, &f.h_sizes, m)) ||
           (r = halloc_mapped(c, &f.h_status, &f.m_status, m)) || (r = halloc_mapped(c, &f.h_res, &f.m_res, res_words(m))))
         return r;
+    if (s->sn_on) {
+      if ((r = dalloc(c, &s->sn_okf, m)) || (r = dalloc(c, &s->sn_cpos, m)) || (r = dalloc(c, &s->sn_ckey, m)) ||
+          (r = dalloc(c, &s->sn_cidx, m)))
+        return r;
+      for (PoolDev::Flight& f : s->fl)
+        if ((r = dalloc(c, &f.d_snd, m)) || (r = halloc(c, &f.h_snd, m))) return r;
+    }
     s->cap_n = m;
-    const size_t tb = txv_pooldev_tmp_bytes(m, std::max<uint32_t>(C, 1));
+    const size_t tb = std::max(txv_pooldev_tmp_bytes(m, std::max<uint32_t>(C, 1)), s->sn_on ? txv_senders_tmp_bytes(m) : (size_t)0);
     if (tb > s->tmp_bytes) {
       if (s->tmp) (void)hipFree(s->tmp);
       s->tmp = nullptr;
@@ -4911,6 +4972,59 @@ int list_ready(txv_ctx* c, PoolDev* s) {
   return TXV_OK;
 }
 
+// ---- the Senders set beside the list (TXV_POOL_SENDERS; senders_dev.h, kernels_senders.hip) ----
+// the set's other buffer has `want` slots (a reallocation waits for the stream: earlier work may
+// still read the buffer)
+int sn_other(txv_ctx* c, PoolDev* s, hipStream_t ks, uint64_t want) {
+  const int nb = s->sn_cur ^ 1;
+  if (s->sn_cap[nb] == want) return TXV_OK;
+  if (ks) HIP_TRY(c, hipStreamSynchronize(ks));
+  s->sn_cap[nb] = 0;
+  if (int r = dalloc(c, &s->sn[nb], want)) return r;
+  s->sn_cap[nb] = want;
+  return TXV_OK;
+}
+
+// the set exists (first use: empty; its size follows the list's expected size, two senders an entry)
+int sn_ready(txv_ctx* c, PoolDev* s) {
+  if (s->sn[s->sn_cur]) return TXV_OK;
+  const uint64_t cap = txv_senders::slots_for(2 * s->list_hint);
+  int r;
+  if ((r = dalloc(c, &s->sn[s->sn_cur], cap))) return r;
+  s->sn_cap[s->sn_cur] = cap;
+  if ((r = sn_other(c, s, nullptr, cap))) return r;
+  HIP_TRY(c, hipMemset(s->sn[s->sn_cur], 0, cap * 8));
+  HIP_TRY(c, hipMemset(s->sn_count, 0, 8));
+  s->sn_bound = 0;
+  return TXV_OK;
+}
+
+// Before a batch of n recorded votes whose words could take the set past half its slots: the set
+// rebuilt on the engine's stream, ahead of the batch, without the words of entries that left the
+// list; if that is not enough, again at twice the size.  The rebuild's own count is waited for (one
+// stream synchronisation per rebuild; a set of S slots is rebuilt at most once per S / 2 recorded
+// votes).
+int sn_rebuild(txv_ctx* c, PoolDev* s, hipStream_t ks, uint32_t n) {
+  const PoolDev::ListBuf& b = s->lb[s->lcur];
+  for (bool first = true;; first = false) {
+    const uint64_t ocap = s->sn_cap[s->sn_cur], want = first ? ocap : 2 * ocap;
+    if (getenv("TXV_PROFILE_HOST"))
+      fprintf(stderr, "[txv pool] senders set rebuild: %llu -> %llu slots, words <= %llu\n", (unsigned long long)ocap,
+              (unsigned long long)want, (unsigned long long)s->sn_bound);
+    if (int r = sn_other(c, s, ks, want)) return r;
+    HIP_TRY(c, txv_senders_rebuild(s->sn[s->sn_cur], ocap, b.fl, nullptr, s->sn[s->sn_cur ^ 1], want, s->seed, s->sn_count, ks));
+    HIP_TRY(c, hipMemcpyAsync(s->h_sn_count, s->sn_count, 8, hipMemcpyDeviceToHost, ks));
+    HIP_TRY(c, hipStreamSynchronize(ks));
+    s->sn_cur ^= 1;
+    s->sn_bound = *s->h_sn_count;
+    ++s->sn_rebuilds;
+    if ((s->sn_bound + n) * 2 > want) continue;
+    // the buffer just left takes the new size too (the stream is idle: nothing reads it), so a later
+    // list compaction or same-size rebuild finds its target allocated and does not wait
+    return sn_other(c, s, nullptr, want);
+  }
+}
+
 // positions ran out (the tail bound + n past the capacity): the live entries (at most live_ub)
 // move, in order, into the other buffer, sized so that at least half of it is free after; the
 // index is rebuilt there without its tombstones
@@ -4939,6 +5053,16 @@ int list_compact(txv_ctx* c, PoolDev* s, hipStream_t ks, uint64_t live_ub, uint3
   }
   HIP_TRY(c, txv_poollist_compact(o.k, o.sz, o.fl, o.ix, o.cap, o.icap, nb.k, nb.sz, nb.fl, nb.ix, nb.cap, nb.icap,
                                   s->lnpos, s->ltmp, s->ltmp_bytes, s->ltail + (s->ltp ^ 1), s->seed, ks));
+  ++s->l_compactions;
+  // the Senders move with their entries: every word of a live entry at its new position, the
+  // dead entries' words dropped (o.fl and lnpos are the old buffer's, as the compaction left them)
+  if (s->sn_on && s->sn[s->sn_cur]) {
+    int r;
+    if ((r = sn_other(c, s, ks, s->sn_cap[s->sn_cur]))) return r;
+    HIP_TRY(c, txv_senders_rebuild(s->sn[s->sn_cur], s->sn_cap[s->sn_cur], o.fl, s->lnpos, s->sn[s->sn_cur ^ 1],
+                                   s->sn_cap[s->sn_cur ^ 1], s->seed, s->sn_count, ks));
+    s->sn_cur ^= 1;
+  }
   s->ltp ^= 1;
   s->lcur ^= 1;
   s->tail_ub = live_ub;
@@ -4947,10 +5071,27 @@ int list_compact(txv_ctx* c, PoolDev* s, hipStream_t ks, uint64_t live_ub, uint3
 
 // the host's pool list becomes the device's: L entries in order (keys [L][32], sizes), ins[e] = 1
 // for the entries txsMap indexes (synchronous, on the engine's own stream)
-int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t* sizes, const uint8_t* ins, uint32_t L) {
+int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t* sizes, const uint8_t* ins, uint32_t L,
+                     const unsigned long long* pairs, size_t n_pairs) {
   HIP_TRY(c, hipSetDevice(s->device));
   s->quiesce();
   int r;
+  // the entries' Senders with them: pairs = (rank in the list, sender) words; the set's image is
+  // built here under the engine's seed and uploaded whole
+  std::vector<txv_senders::word_t> img;
+  if (s->sn_on) {
+    if ((r = sn_ready(c, s))) return r;
+    uint64_t cap = s->sn_cap[s->sn_cur];
+    while (n_pairs * 2 > cap) cap *= 2;
+    if (cap != s->sn_cap[s->sn_cur]) {
+      s->sn_cur ^= 1;                                  // (sn_other fills the other buffer)
+      if ((r = sn_other(c, s, nullptr, cap))) return r;
+      s->sn_cur ^= 1;
+      if ((r = sn_other(c, s, nullptr, cap))) return r;
+    }
+    if (n_pairs) img.assign(cap, 0);                   // (an empty set is a fill on the device)
+    for (size_t k = 0; k < n_pairs; ++k) (void)txv_senders::insert(img.data(), cap - 1, pairs[k], s->seed);
+  }
   const uint32_t cap = std::max(list_cap_for(2 * ((uint64_t)L + 4 * (uint64_t)s->cap_n)), list_cap_initial(s));
   if (!cap) { c->err = "pool list above 2^30 entries"; return TXV_ECAPACITY; }
   PoolDev::ListBuf& b = s->lb[s->lcur];
@@ -4968,6 +5109,14 @@ int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t
   HIP_TRY(c, txv_poollist_upload_index(b.k, d_ins, L, b.ix, b.icap, s->seed, s->st));
   s->h_clen[0] = L;                                    // (staging word)
   HIP_TRY(c, hipMemcpyAsync(s->ltail + s->ltp, s->h_clen, 4, hipMemcpyHostToDevice, s->st));
+  if (s->sn_on) {
+    *s->h_sn_count = n_pairs;
+    if (n_pairs) HIP_TRY(c, hipMemcpyAsync(s->sn[s->sn_cur], img.data(), img.size() * 8, hipMemcpyHostToDevice, s->st));
+    else HIP_TRY(c, hipMemsetAsync(s->sn[s->sn_cur], 0, s->sn_cap[s->sn_cur] * 8, s->st));
+    HIP_TRY(c, hipMemcpyAsync(s->sn_count, s->h_sn_count, 8, hipMemcpyHostToDevice, s->st));
+    s->sn_bound = n_pairs;
+    for (PoolDev::Flight& f : s->fl) f.sn_mark = 0;
+  }
   HIP_TRY(c, hipStreamSynchronize(s->st));
   dfree(d_ins);
   s->tail_ub = L;
@@ -4977,8 +5126,9 @@ int pooldev_list_put(txv_ctx* c, PoolDev* s, const uint8_t* keys, const uint32_t
 // the device's pool list, in order: its live entries' keys, sizes and whether txsMap indexes
 // them (synchronous; c may be NULL)
 int pooldev_list_get(txv_ctx* c, PoolDev* s, std::vector<uint8_t>& keys, std::vector<uint32_t>& sizes,
-                     std::vector<uint8_t>& ins) {
+                     std::vector<uint8_t>& ins, std::vector<unsigned long long>* pairs) {
   keys.clear(); sizes.clear(); ins.clear();
+  if (pairs) pairs->clear();
   const PoolDev::ListBuf& b = s->lb[s->lcur];
   if (!b.cap) return TXV_OK;
   if (hipSetDevice(s->device) != hipSuccess) return TXV_EDEVICE;
@@ -5002,11 +5152,25 @@ int pooldev_list_get(txv_ctx* c, PoolDev* s, std::vector<uint8_t>& keys, std::ve
   std::vector<uint8_t> indexed(T, 0);
   for (unsigned long long v : ix)
     if (v && (uint32_t)v != kListTomb && (uint32_t)v - 1 < T) indexed[(uint32_t)v - 1] = 1;
+  std::vector<uint32_t> rank(pairs ? T : 0);
   for (uint32_t e = 0; e < T; ++e) {
+    if (pairs) rank[e] = (uint32_t)sizes.size();
     if (!fl[e]) continue;
     keys.insert(keys.end(), k.begin() + (size_t)e * 32, k.begin() + (size_t)e * 32 + 32);
     sizes.push_back(sz[e]);
     ins.push_back(indexed[e]);
+  }
+  // the live entries' Senders, each word renamed to its entry's rank in the list that goes home
+  if (pairs && s->sn_on && s->sn[s->sn_cur]) {
+    std::vector<txv_senders::word_t> img(s->sn_cap[s->sn_cur]);
+    if (!ok(hipMemcpyAsync(img.data(), s->sn[s->sn_cur], img.size() * 8, hipMemcpyDeviceToHost, s->st)) ||
+        !ok(hipStreamSynchronize(s->st)))
+      return TXV_EDEVICE;
+    for (txv_senders::word_t w : img) {
+      if (!w) continue;
+      const uint64_t e = txv_senders::word_entry(w);
+      if (e < T && fl[e]) pairs->push_back(txv_senders::pair_word(rank[e], txv_senders::word_sender(w)));
+    }
   }
   return TXV_OK;
 }
@@ -5135,7 +5299,8 @@ int update_list_keys(txv_ctx* c, uint64_t ticket, uint32_t n, std::vector<uint8_
 int pooldev_enqueue(txv_ctx* c, PoolDev* s, int slot, const txv_votes* v, const uint8_t* h_keys_in,
                     const uint32_t* h_sizes, const uint32_t* d_keys, const uint32_t* d_sizes, const uint8_t* d_valid,
                     uint32_t valid_ok, uint32_t n, int64_t max_tx, bool wal, bool keys_back, void* after_ev,
-                    bool list_on, uint64_t live_ub, uint32_t n_upd, uint8_t* d_status_copy, void* then_stream) {
+                    bool list_on, uint64_t live_ub, uint32_t n_upd, uint8_t* d_status_copy, void* then_stream,
+                    const uint16_t* h_senders) {
   hipEvent_t after = (hipEvent_t)after_ev;
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t total = n_upd + n;
@@ -5225,7 +5390,35 @@ int pooldev_enqueue(txv_ctx* c, PoolDev* s, int slot, const txv_votes* v, const 
     f.nt_app = (total + 1023) / 1024;
     f.nt_rm = (n_upd + 1023) / 1024;
   }
-  HIP_TRY(c, txv_pooldev_run(&a, ks));
+  // TXV_POOL_SENDERS: the batch's sender column into the slot (h_senders null: CheckTx's
+  // UnknownPeerID 0 for every vote, a fill), the set rebuilt first if the batch could fill it
+  SendersArgs sa{};
+  const bool record = list_on && s->sn_on && n;
+  f.sn_mark = 0;
+  if (record) {
+    int r;
+    if ((r = sn_ready(c, s))) return r;
+    if ((s->sn_bound + n) * 2 > s->sn_cap[s->sn_cur] && (r = sn_rebuild(c, s, ks, n))) return r;
+    if (h_senders) {
+      memcpy(f.h_snd, h_senders, (size_t)n * 2);
+      HIP_TRY(c, hipMemcpyAsync(f.d_snd, f.h_snd, (size_t)n * 2, hipMemcpyHostToDevice, ks));
+    } else {
+      HIP_TRY(c, hipMemsetAsync(f.d_snd, 0, (size_t)n * 2, ks));
+    }
+    sa.n = total; sa.n_force = n_upd; sa.keys = d_keys; sa.status = f.d_status; sa.okpos = s->okpos;
+    sa.skey = s->skey; sa.sidx = s->sidx; sa.senders = f.d_snd;
+    sa.lk = a.l.lk; sa.li = a.l.li; sa.imask = a.l.imask; sa.tail_in = a.l.tail_in; sa.seed = s->seed;
+    sa.okf = s->sn_okf; sa.cpos = s->sn_cpos; sa.ckey = s->sn_ckey; sa.cidx = s->sn_cidx;
+    sa.tmp = s->tmp; sa.tmp_bytes = s->tmp_bytes;
+    sa.slots = s->sn[s->sn_cur]; sa.mask = s->sn_cap[s->sn_cur] - 1; sa.count = s->sn_count;
+  }
+  HIP_TRY(c, txv_pooldev_run(&a, record ? &sa : nullptr, ks));
+  if (record) {   // the set's exact word count after this batch, for the host's bound
+    HIP_TRY(c, hipMemcpyAsync(f.h_sn, s->sn_count, 8, hipMemcpyDeviceToHost, ks));
+    s->sn_bound += n;
+    s->sn_enq += n;
+    f.sn_mark = s->sn_enq;
+  }
   if (s->C) s->cur ^= 1;                                  // the next batch on this stream reads the new cache
   if (list_on) {                                          // pd_status wrote the tail's other word
     s->ltp ^= 1;
@@ -5256,6 +5449,66 @@ int pooldev_finish(txv_ctx* c, PoolDev* s, int slot, const uint8_t** status, con
   if (keys) *keys = reinterpret_cast<const uint8_t*>(f.h_keys);
   if (sizes) *sizes = f.h_sizes;
   return TXV_OK;
+}
+
+// slot's finished batch reported the set's exact word count: the bound is that plus the votes
+// enqueued since (with the pool's lock held: list_counts)
+void pooldev_senders_finish(PoolDev* s, int slot) {
+  PoolDev::Flight& f = s->fl[slot];
+  if (!f.sn_mark) return;
+  s->sn_bound = std::min<uint64_t>(s->sn_bound, (uint64_t)*f.h_sn + (s->sn_enq - f.sn_mark));
+  f.sn_mark = 0;
+}
+
+// test hook (txv_pool_senders_stats)
+void pooldev_senders_stats(const PoolDev* s, uint64_t out[4]) {
+  out[0] = s->sn_bound; out[1] = s->sn_cap[s->sn_cur]; out[2] = s->sn_rebuilds; out[3] = s->l_compactions;
+}
+
+// txv_pool_sent_by / txv_pool_ticket_sent_by on the device (every batch finished by the caller;
+// synchronous, on the engine's own stream): h_keys [n][32], or -- null -- the keys and statuses of
+// pool ticket `id` where they lie in its flight slot (1: no slot holds them any more, or it is a
+// routed batch, whose keys were never in the slot)
+int pooldev_sent_by(txv_ctx* c, PoolDev* s, const uint8_t* h_keys, uint64_t id, uint32_t n, const uint16_t* peers,
+                    uint32_t n_peers, uint32_t* bits_out) {
+  HIP_TRY(c, hipSetDevice(s->device));
+  const uint32_t* d_keys = nullptr;
+  const uint8_t* d_status = nullptr;
+  if (!h_keys) {
+    const PoolDev::Flight* hit = nullptr;
+    for (const PoolDev::Flight& f : s->fl)
+      if (id && f.occ == id) hit = &f;
+    if (!hit || hit->occ_routed) return 1;
+    n = hit->occ_n;
+    d_keys = hit->d_keys + (size_t)hit->occ_upd * 8;
+    d_status = hit->d_status + hit->occ_upd;
+  }
+  const uint32_t W = (n_peers + 31) / 32;
+  if (!n) return 0;
+  const PoolDev::ListBuf& b = s->lb[s->lcur];
+  if (!b.cap || !s->sn[s->sn_cur]) {   // nothing was ever recorded
+    memset(bits_out, 0, (size_t)n * W * 4);
+    return 0;
+  }
+  s->quiesce();
+  uint32_t *dk = nullptr, *dbits = nullptr;
+  uint16_t* dp = nullptr;
+  int r;
+  auto done = [&](int rc) { dfree(dk); dfree(dp); dfree(dbits); return rc; };
+  if ((h_keys && (r = dalloc(c, &dk, (size_t)n * 8))) || (r = dalloc(c, &dp, n_peers)) || (r = dalloc(c, &dbits, (size_t)n * W)))
+    return done(r);
+  auto ok = [&](hipError_t e) {
+    if (e != hipSuccess) c->err = std::string("pool senders query: ") + hipGetErrorString(e);
+    return e == hipSuccess;
+  };
+  if ((h_keys && !ok(hipMemcpyAsync(dk, h_keys, (size_t)n * 32, hipMemcpyHostToDevice, s->st))) ||
+      !ok(hipMemcpyAsync(dp, peers, (size_t)n_peers * 2, hipMemcpyHostToDevice, s->st)) ||
+      !ok(txv_senders_query(h_keys ? dk : d_keys, d_status, n, dp, n_peers, b.k, b.ix, b.icap - 1, s->sn[s->sn_cur],
+                            s->sn_cap[s->sn_cur] - 1, s->seed, dbits, s->st)) ||
+      !ok(hipMemcpyAsync(bits_out, dbits, (size_t)n * W * 4, hipMemcpyDeviceToHost, s->st)) ||
+      !ok(hipStreamSynchronize(s->st)))
+    return done(TXV_EDEVICE);
+  return done(0);
 }
 
 // flight slot `slot` holds pool ticket `id`'s batch (n votes after n_upd Update entries): a TxFlow
@@ -5551,11 +5804,11 @@ int txv_ctx_fail(txv_ctx* c, int code, const char* msg) {
 int pooldev_check(txv_ctx* c, PoolDev* s, const txv_votes* v, const uint8_t* h_keys_in, const uint32_t* h_sizes,
                   const uint32_t* d_keys, const uint32_t* d_sizes, const uint8_t* d_valid, uint32_t valid_ok, uint32_t n,
                   int64_t max_tx, bool wal, uint8_t* keys_out, uint8_t* status_out, void* after_ev, bool list_on,
-                  uint64_t live_ub, int slot, uint32_t n_upd) {
+                  uint64_t live_ub, int slot, uint32_t n_upd, const uint16_t* h_senders) {
   if (!n) return TXV_OK;
   HostTimer ht(c->profile_host);
   int r = pooldev_enqueue(c, s, slot, v, h_keys_in, h_sizes, d_keys, d_sizes, d_valid, valid_ok, n, max_tx, wal,
-                          keys_out != nullptr, after_ev, list_on, live_ub, n_upd, nullptr, nullptr);
+                          keys_out != nullptr, after_ev, list_on, live_ub, n_upd, nullptr, nullptr, h_senders);
   if (r) return r;
   ht.mark("enqueue");
   const uint8_t* st;

@@ -293,6 +293,16 @@ def lib():
             "txv_pool_check_routed": ([vp, vp, vp, vp, vp], ctypes.c_int),
             "txv_submit_routed_checked": ([vp, vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
                                           ctypes.c_int),
+            "txv_pool_check_submit_from": ([vp, vp, ctypes.POINTER(_Votes), vp, vp, vp,
+                                            ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_pool_check_from": ([vp, vp, ctypes.POINTER(_Votes), vp, vp, vp, vp], ctypes.c_int),
+            "txv_pool_check_keys_from": ([vp, vp, vp, vp, u32, vp, vp], ctypes.c_int),
+            "txv_pool_receive_from": ([vp, vp, vp, ctypes.c_uint64, vp, vp, u32, vp, vp, vp], ctypes.c_int),
+            "txv_ingest_decode_from": ([vp, vp, vp, ctypes.c_uint64, vp, vp, u32, vp,
+                                        ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_pool_sent_by": ([vp, vp, vp, u32, vp, u32, vp], ctypes.c_int),
+            "txv_pool_ticket_sent_by": ([vp, vp, ctypes.c_uint64, vp, u32, vp], ctypes.c_int),
+            "txv_pool_senders_stats": ([vp, vp], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -327,7 +337,9 @@ EXPORTED_SYMBOLS = [
     "txv_gossip_sink_enable", "txv_gossip_msgs",
     "txv_sign_txs_bytes", "txv_sign_txs_submit", "txv_sign_txs_wait", "txv_sign_txs", "txv_sign_txs_ms",
     "txv_scalarmult_base",
-    "txv_sign_txs_meta", "txv_pool_check_routed_submit", "txv_pool_check_routed", "txv_submit_routed_checked"]
+    "txv_sign_txs_meta", "txv_pool_check_routed_submit", "txv_pool_check_routed", "txv_submit_routed_checked",
+    "txv_pool_check_submit_from", "txv_pool_check_from", "txv_pool_check_keys_from", "txv_pool_receive_from",
+    "txv_ingest_decode_from", "txv_pool_sent_by", "txv_pool_ticket_sent_by", "txv_pool_senders_stats"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -1312,6 +1324,23 @@ POOL_NO_CACHE = 0xFFFFFFFF
 POOL_WAL = 0x1      # TXV_POOL_WAL
 SUBMIT_RING = 4         # txv_submit_votes batches in flight (staged slots 0 .. 3)
 POOL_DEVICE_CACHE = 0x2   # TXV_POOL_DEVICE_CACHE: the LRU cache in HBM, CheckTx decisions on the GPU
+POOL_SENDERS = 0x4        # TXV_POOL_SENDERS: the pool keeps every entry's MempoolTxVote.Senders
+
+
+def _sender_col(senders, n: int, what: str):
+    """a senders= argument as the contiguous u16 column the *_from calls take (None stays None)"""
+    if senders is None:
+        return None
+    col = np.ascontiguousarray(senders, np.uint16)
+    if col.shape != (n,):
+        raise ValueError(f"{what}: senders must hold one peer id per vote ({n}), got shape {col.shape}")
+    return col
+
+
+def _unpack_rows(bits: np.ndarray, k: int) -> np.ndarray:
+    """[n, ceil(k / 32)] u32 bit rows -> bool [n, k]"""
+    b = np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")
+    return b[:, :k].astype(bool)
 
 
 class _RoutedBatch:
@@ -1327,17 +1356,22 @@ class TxVotePool:
     Update (:329-359), ReapMaxTxs (:310-324), Flush (:146-159), Size (:136), TxsBytes (:141).
     cache_size POOL_NO_CACHE selects nopTxCache; 0 fields take tendermint's defaults.
     device_cache: TXV_POOL_DEVICE_CACHE (include/txvote.h) -- the cache lives in the HBM of
-    ctx's GPU and each batch's CheckTx decisions are made there."""
+    ctx's GPU and each batch's CheckTx decisions are made there.
+    senders: TXV_POOL_SENDERS -- CheckTxWithInfo's TxInfo.SenderID is recorded per entry
+    (senders= on check_batch / check_submit / check_keys / receive / ingest_decode) and sent_by
+    answers broadcastTxRoutine's "has this peer sent us this vote" (reactor.go:245)."""
 
     def __init__(self, ctx: Optional[Context], size: int = 0, cache_size: int = 0, max_txs_bytes: int = 0,
-                 max_msg_bytes: int = 0, height: int = 0, wal: bool = False, device_cache: bool = False):
+                 max_msg_bytes: int = 0, height: int = 0, wal: bool = False, device_cache: bool = False,
+                 senders: bool = False):
         self.ctx = ctx
         if ctx is not None:
             if not hasattr(ctx, "_pools"):
                 ctx._pools = weakref.WeakSet()
             ctx._pools.add(self)
         cfg = _PoolCfg(size, cache_size, max_txs_bytes, max_msg_bytes,
-                       (POOL_WAL if wal else 0) | (POOL_DEVICE_CACHE if device_cache else 0))
+                       (POOL_WAL if wal else 0) | (POOL_DEVICE_CACHE if device_cache else 0) |
+                       (POOL_SENDERS if senders else 0))
         h = ctypes.c_void_p()
         rc = lib().txv_pool_new(ctypes.byref(cfg), height, ctypes.byref(h))
         if rc != 0:
@@ -1357,15 +1391,22 @@ class TxVotePool:
     def __del__(self):
         self.close()
 
-    def check_batch(self, batch: VoteBatch, long_sigs: Optional[dict] = None) -> np.ndarray:
+    def check_batch(self, batch: VoteBatch, long_sigs: Optional[dict] = None, senders=None) -> np.ndarray:
         out = np.zeros(max(batch.n, 1), np.uint8)
         full, off = _long_sig_arena(batch, long_sigs)
         vs = batch.c_struct()
         ctx = self._ctx_or_raise("check_batch")
-        ctx._chk(lib().txv_pool_check(self._h, ctx._h, ctypes.byref(vs), full, off, out.ctypes.data), "txv_pool_check")
+        snd = _sender_col(senders, batch.n, "check_batch")
+        if snd is None:
+            ctx._chk(lib().txv_pool_check(self._h, ctx._h, ctypes.byref(vs), full, off, out.ctypes.data), "txv_pool_check")
+        else:
+            ctx._chk(lib().txv_pool_check_from(self._h, ctx._h, ctypes.byref(vs), full, off, snd.ctypes.data,
+                                               out.ctypes.data), "txv_pool_check_from")
         return out[:batch.n]
 
-    def check_submit(self, batch: VoteBatch, long_sigs: Optional[dict] = None) -> int:
+    check = check_batch
+
+    def check_submit(self, batch: VoteBatch, long_sigs: Optional[dict] = None, senders=None) -> int:
         """txv_pool_check_submit: the batch is CheckTx'd in submission order; with the device cache
         its decisions are enqueued on the GPU and the call returns (check_wait(ticket) gives the
         statuses).  The batch's columns are kept referenced until the wait."""
@@ -1373,11 +1414,16 @@ class TxVotePool:
         full, off = _long_sig_arena(batch, long_sigs)
         vs = batch.c_struct()
         t = ctypes.c_uint64(0)
-        ctx._chk(lib().txv_pool_check_submit(self._h, ctx._h, ctypes.byref(vs), full, off, ctypes.byref(t)),
-                 "txv_pool_check_submit")
+        snd = _sender_col(senders, batch.n, "check_submit")
+        if snd is None:
+            ctx._chk(lib().txv_pool_check_submit(self._h, ctx._h, ctypes.byref(vs), full, off, ctypes.byref(t)),
+                     "txv_pool_check_submit")
+        else:
+            ctx._chk(lib().txv_pool_check_submit_from(self._h, ctx._h, ctypes.byref(vs), full, off, snd.ctypes.data,
+                                                      ctypes.byref(t)), "txv_pool_check_submit_from")
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, vs, full, off)
+        self._inflight[t.value] = (batch, vs, full, off, snd)
         return t.value
 
     def check_wait(self, ticket: int) -> np.ndarray:
@@ -1436,28 +1482,84 @@ class TxVotePool:
                                         sizes.ctypes.data), "txv_pool_prepare")
         return keys[:n], sizes[:n]
 
-    def check_keys(self, keys: np.ndarray, sizes: np.ndarray) -> np.ndarray:
+    def check_keys(self, keys: np.ndarray, sizes: np.ndarray, senders=None) -> np.ndarray:
         """CheckTxWithInfo over (txVoteKey [n, 32] u8, TxVote.Size() [n] u32) pairs in arrival order
-        (txv_pool_check_keys); needs no GPU when the pool was made with ctx=None"""
+        (txv_pool_check_keys; with senders= [n] u16 peer ids, txv_pool_check_keys_from); needs no
+        GPU when the pool was made with ctx=None"""
         keys = np.ascontiguousarray(keys, np.uint8)
         sizes = np.ascontiguousarray(sizes, np.uint32)
         n = len(sizes)
         out = np.zeros(max(n, 1), np.uint8)
-        rc = lib().txv_pool_check_keys(self._h, self.ctx._h if self.ctx is not None else None, keys.ctypes.data,
-                                       sizes.ctypes.data, n, out.ctypes.data)
+        ch = self.ctx._h if self.ctx is not None else None
+        snd = _sender_col(senders, n, "check_keys")
+        if snd is None:
+            rc = lib().txv_pool_check_keys(self._h, ch, keys.ctypes.data, sizes.ctypes.data, n, out.ctypes.data)
+        else:
+            rc = lib().txv_pool_check_keys_from(self._h, ch, keys.ctypes.data, sizes.ctypes.data, n, snd.ctypes.data,
+                                                out.ctypes.data)
         if rc != 0:
-            raise TxvInfraError(f"txv_pool_check_keys failed ({rc})")
+            raise TxvInfraError(f"txv_pool_check_keys{'_from' if snd is not None else ''} failed ({rc})")
         return out[:n]
 
-    def receive(self, wb: WireBatch):
+    def receive(self, wb: WireBatch, senders=None):
         """Reactor.Receive (txvotepool/reactor.go:170-190) for a batch of messages in arrival order:
-        (wire status TXV_WIRE_*, pool status TXV_POOL_* or POOL_NOT_CHECKED) per message."""
+        (wire status TXV_WIRE_*, pool status TXV_POOL_* or POOL_NOT_CHECKED) per message.
+        senders= [n] u16: the id of the peer each message came from (txv_pool_receive_from)."""
         ws = np.zeros(max(wb.n, 1), np.uint8)
         ps = np.zeros(max(wb.n, 1), np.uint8)
         ctx = self._ctx_or_raise("receive")
-        ctx._chk(lib().txv_pool_receive(self._h, ctx._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
-                                        wb.len.ctypes.data, wb.n, ws.ctypes.data, ps.ctypes.data), "txv_pool_receive")
+        snd = _sender_col(senders, wb.n, "receive")
+        if snd is None:
+            ctx._chk(lib().txv_pool_receive(self._h, ctx._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
+                                            wb.len.ctypes.data, wb.n, ws.ctypes.data, ps.ctypes.data), "txv_pool_receive")
+        else:
+            ctx._chk(lib().txv_pool_receive_from(self._h, ctx._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
+                                                 wb.len.ctypes.data, wb.n, snd.ctypes.data, ws.ctypes.data,
+                                                 ps.ctypes.data), "txv_pool_receive_from")
         return ws[:wb.n], ps[:wb.n]
+
+    def sent_by(self, keys: np.ndarray, peers) -> np.ndarray:
+        """txv_pool_sent_by: bool [n, n_peers]; [i, p] is True iff the pool holds key i now and
+        peers[p] is in that entry's Senders (what broadcastTxRoutine asks before a send,
+        reactor.go:245).  Finishes every submitted batch and Update first."""
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, 32)
+        peers = np.ascontiguousarray(peers, np.uint16).reshape(-1)
+        n, k = len(keys), len(peers)
+        w = (k + 31) // 32
+        bits = np.zeros((max(n, 1), max(w, 1)), np.uint32)
+        rc = lib().txv_pool_sent_by(self._h, self.ctx._h if self.ctx is not None else None, keys.ctypes.data, n,
+                                    peers.ctypes.data, k, bits.ctypes.data)
+        if rc != 0:
+            raise TxvInfraError(f"txv_pool_sent_by failed ({rc})")
+        return _unpack_rows(bits[:n], k)
+
+    def ticket_sent_by(self, ticket: int, peers, n: Optional[int] = None) -> np.ndarray:
+        """txv_pool_ticket_sent_by: sent_by's rows for the votes of a check_submit ticket (zero rows
+        for the votes it did not admit), the keys read in the device engine's flight slot.  n: the
+        ticket's batch size -- needed once the ticket was waited (before, the batch is at hand).
+        TxvInfraError (-1, TXV_ESTATE) when the ticket holds no flight slot: use sent_by."""
+        ctx = self._ctx_or_raise("ticket_sent_by")
+        peers = np.ascontiguousarray(peers, np.uint16).reshape(-1)
+        if n is None:
+            ent = getattr(self, "_inflight", {}).get(ticket)
+            if ent is None:
+                raise ValueError(f"ticket_sent_by: ticket {ticket} was waited (or is unknown): pass its batch size n")
+            n = ent[0].n
+        k = len(peers)
+        bits = np.zeros((max(n, 1), max((k + 31) // 32, 1)), np.uint32)
+        rc = lib().txv_pool_ticket_sent_by(self._h, ctx._h, ticket, peers.ctypes.data, k, bits.ctypes.data)
+        if rc != 0:
+            raise TxvInfraError(f"txv_pool_ticket_sent_by failed ({rc})")
+        return _unpack_rows(bits[:n], k)
+
+    def senders_stats(self):
+        """txv_pool_senders_stats (test hook): (words stored, slots, set rebuilds, compactions of the
+        list in HBM, 1 when the list and its sets are in HBM now)"""
+        st = np.zeros(5, np.uint64)
+        rc = lib().txv_pool_senders_stats(self._h, st.ctypes.data)
+        if rc != 0:
+            raise TxvInfraError(f"txv_pool_senders_stats failed ({rc})")
+        return tuple(int(x) for x in st)
 
     def _ctx_or_raise(self, what: str):
         if self.ctx is None:
@@ -1503,12 +1605,19 @@ class TxVotePool:
                  "txv_ingest_submit")
         return IngestTicket(t.value, n, ws[:n], ps[:n])
 
-    def ingest_decode(self, wb: WireBatch) -> IngestTicket:
-        """txv_ingest_decode: upload + decode + keys enqueued (returns at once); ingest_admit next"""
+    def ingest_decode(self, wb: WireBatch, senders=None) -> IngestTicket:
+        """txv_ingest_decode: upload + decode + keys enqueued (returns at once); ingest_admit next.
+        senders= [n] u16: the messages' peer ids (txv_ingest_decode_from), used by the admit"""
         ctx = self._ctx_or_raise("ingest_decode")
         t = ctypes.c_uint64()
-        ctx._chk(lib().txv_ingest_decode(ctx._h, self._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
-                                         wb.len.ctypes.data, wb.n, ctypes.byref(t)), "txv_ingest_decode")
+        snd = _sender_col(senders, wb.n, "ingest_decode")
+        if snd is None:
+            ctx._chk(lib().txv_ingest_decode(ctx._h, self._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
+                                             wb.len.ctypes.data, wb.n, ctypes.byref(t)), "txv_ingest_decode")
+        else:
+            ctx._chk(lib().txv_ingest_decode_from(ctx._h, self._h, wb.wire.ctypes.data, wb.nbytes, wb.off.ctypes.data,
+                                                  wb.len.ctypes.data, wb.n, snd.ctypes.data, ctypes.byref(t)),
+                     "txv_ingest_decode_from")
         n = wb.n
         return IngestTicket(t.value, n, np.zeros(n, np.uint8), np.zeros(n, np.uint8))
 

@@ -308,7 +308,8 @@ int txv_store_records(txv_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap,
  * txv_submit_checked the non-nil votes are exactly those the pool admitted, and arrival order is
  * the order broadcastTxRoutine walks the pool list.  The chain runs on the flow stream before the
  * batch's tally, while that stream waits for the batch's verify; it touches no TxFlow state.  The
- * send itself, and the per-entry sender sets (txvotepool.go:213-250), stay the caller's.  The
+ * send itself stays the caller's, and so do the per-entry sender sets (txvotepool.go:213-250)
+ * unless the pool keeps them (TXV_POOL_SENDERS: txv_pool_ticket_sent_by answers :245).  The
  * Update, store and gossip sinks may all be on at once.
  * Entry flags:
  *   TXV_GOSSIP_OK           the message is in the buffer
@@ -327,7 +328,8 @@ int txv_store_records(txv_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap,
  *   into the slot while a read-out is copying fails with TXV_ESTATE, and so does a second read-out
  *   of the slot meanwhile).  out = the buffer as built: message k at off_out[k], a multiple of 16,
  *   len_out[k] bytes long, zero padding up to the next message; idx_out[k] = the vote's index in
- *   the batch (the caller keeps its own sender ids and skips the peer that sent vote idx);
+ *   the batch (the caller skips the peers txv_pool_ticket_sent_by reports for vote idx, or, with
+ *   a pool that keeps no Senders, the peer its own record names as the sender of vote idx);
  *   flag_out[k] as above.  Any output may be NULL; *n_out = entries, *bytes_out = buffer bytes.
  *   Only the bytes and descriptors used are copied, on a stream of the read-out's own and without
  *   the context's lock, so batches in flight are not stalled.
@@ -652,6 +654,12 @@ typedef struct {
  * is fetched back first and uploaded again by the next device batch.  The device copy is freed with
  * the pool. */
 #define TXV_POOL_DEVICE_CACHE 0x2u
+/* The pool keeps MempoolTxVote.Senders (txvotepool.go:364-371) for every entry of its list: see
+ * "CheckTxWithInfo's senders" below.  Without the flag nothing is kept, no memory is allocated, no
+ * kernel is enqueued and every call behaves as before.  With TXV_POOL_DEVICE_CACHE the sets live in
+ * HBM beside the pool list, are written by each device batch's engine chain, and move between host
+ * and device with the list. */
+#define TXV_POOL_SENDERS 0x4u
 #define TXV_POOL_NO_CACHE 0xFFFFFFFFu
 typedef struct txv_pool txv_pool;
 
@@ -818,6 +826,55 @@ int txv_pool_sync(txv_pool* pool);
 /* LRU cache keys front (oldest) to back; *n_out = cache length (test hook: cache_test.go). */
 int txv_pool_cache_keys(txv_pool* pool, uint8_t* keys_out, uint64_t cap, uint64_t* n_out);
 
+/* ---- CheckTxWithInfo's senders (TXV_POOL_SENDERS) ----
+ * CheckTxWithInfo(tx, cb, TxInfo{SenderID}) differs from CheckTx in one thing: the pool entry
+ * remembers which peers sent the vote (MempoolTxVote.Senders), so broadcastTxRoutine does not send
+ * it back to them (txvotepool/reactor.go:245).  For each vote of a batch in arrival order, with
+ * sender id s (0 = UnknownPeerID):
+ *   TXV_POOL_OK            the new entry's set is {s}                               (:250)
+ *   TXV_POOL_ERR_IN_CACHE  if txsMap holds the vote's key at that moment, s joins that entry's
+ *                          set; otherwise nothing (a committed vote is cached, not pooled) (:213-227)
+ *   every other status     nothing (ERR_ENCODING is returned before addTx: no entry exists)
+ * Update's committed votes remove entries together with their sets and record no sender;
+ * txv_pool_flush empties all sets.  The calls without a sender argument (txv_pool_check*,
+ * txv_pool_check_routed*, txv_pool_receive, txv_ingest_*) record sender 0, as CheckTx does
+ * (:180-182).  "At that moment" holds inside a batch too: a key admitted, hit, evicted from the
+ * cache, admitted again and hit again within one batch leaves the first hit's sender with the
+ * first entry and the second's with the second (the one txsMap indexes afterwards).
+ * The *_from calls are their namesakes with a sender column: senders == NULL = all 0; senders[i]
+ * is read even for a vote that ends up not checked; on a pool without TXV_POOL_SENDERS a non-NULL
+ * column returns TXV_ESTATE and touches nothing.  txv_ingest_decode_from copies the column before
+ * it returns; the ticket's admit (txv_ingest_admit, or the _admit_submit / _admit_finish pair)
+ * uses it.
+ * txv_pool_sent_by: bits_out = [n][ceil(n_peers / 32)] words; bit p of row i is set iff txsMap holds
+ *   key i now -- after every batch and Update submitted so far, which the call finishes first, as
+ *   every reader of the pool list does -- and peers[p] is in that entry's Senders.  A key not in
+ *   the pool gives a zero row.  ctx is optional, as for txv_pool_check_keys.  TXV_ESTATE without
+ *   the flag, TXV_EINVAL for null arguments or n_peers == 0.  Takes the pool's lock, then the
+ *   context's (the order of txv_submit_checked).
+ * txv_pool_ticket_sent_by: the same rows for the votes of a CheckTx ticket, with the keys read
+ *   where they lie in the device engine's flight slot (only the rows of votes the ticket admitted
+ *   are filled; a row is looked up by key, so a vote re-admitted later under the same key reports
+ *   the later entry, as txsMap.Load does).  The call finishes the ticket, and every batch
+ *   submitted so far, first.  TXV_ESTATE when the ticket no longer holds its flight slot (eight
+ *   later batches have taken the ring's slots), was decided on the host, or is a routed batch
+ *   (its keys were never in the slot): the caller then uses the key form.  This is what a node on
+ *   the device path calls before it gossips a batch: it never sees keys.
+ * txv_pool_senders_stats (test hook): stats_out = {words stored in the set, those of entries
+ *   that left the list included (in HBM: the host's upper bound); slots; rebuilds of the set so
+ *   far; compactions of the list in HBM so far; 1 when the list and its sets are in HBM now}. */
+int txv_pool_check_submit_from(txv_pool* pool, txv_ctx* ctx, const txv_votes* votes, const uint8_t* sig_full,
+                               const uint64_t* sig_full_off, const uint16_t* senders, uint64_t* ticket);
+int txv_pool_check_from(txv_pool* pool, txv_ctx* ctx, const txv_votes* votes, const uint8_t* sig_full,
+                        const uint64_t* sig_full_off, const uint16_t* senders, uint8_t* status_out);
+int txv_pool_check_keys_from(txv_pool* pool, txv_ctx* ctx, const uint8_t* keys32, const uint32_t* sizes, uint32_t n,
+                             const uint16_t* senders, uint8_t* status_out);
+int txv_pool_sent_by(txv_pool* pool, txv_ctx* ctx, const uint8_t* keys32, uint32_t n, const uint16_t* peers,
+                     uint32_t n_peers, uint32_t* bits_out);
+int txv_pool_ticket_sent_by(txv_pool* pool, txv_ctx* ctx, uint64_t pool_ticket, const uint16_t* peers,
+                            uint32_t n_peers, uint32_t* bits_out);
+int txv_pool_senders_stats(txv_pool* pool, uint64_t stats_out[5]);
+
 /* ---- TxVoteMessage wire decode (Reactor.Receive, txvotepool/reactor.go:170-190, 273-291) ----
  * n received messages (message i = wire[msg_off[i] .. + msg_len[i]), wire < 4 GiB) decoded on
  * the GPU, amino UnmarshalBinaryBare of the TxpoolMessage interface whose one registered
@@ -866,6 +923,11 @@ int txv_encode_msgs(const txv_votes* votes, const uint8_t* txkey, const uint8_t*
 int txv_pool_receive(txv_pool* pool, txv_ctx* ctx, const uint8_t* wire, uint64_t wire_bytes,
                      const uint64_t* msg_off, const uint32_t* msg_len, uint32_t n, uint8_t* wire_status_out,
                      uint8_t* pool_status_out);
+/* txv_pool_receive with senders[i] = the id of the peer message i came from (Receive's
+ * txInfo.SenderID, reactor.go:183-188); "CheckTxWithInfo's senders" above */
+int txv_pool_receive_from(txv_pool* pool, txv_ctx* ctx, const uint8_t* wire, uint64_t wire_bytes,
+                          const uint64_t* msg_off, const uint32_t* msg_len, uint32_t n, const uint16_t* senders,
+                          uint8_t* wire_status_out, uint8_t* pool_status_out);
 /* The whole ingest chain for n received messages in arrival order, device-resident:
  *   Reactor.Receive / decodeMsg (txvotepool/reactor.go:170-190, 278-284)
  *   -> TxVotePool.CheckTxWithInfo (txvotepool/txvotepool.go:187-261) for every decoded vote
@@ -917,6 +979,11 @@ int txv_ingest_submit(txv_ctx* ctx, txv_pool* pool, const uint8_t* wire, uint64_
 int txv_ingest_decode(txv_ctx* ctx, txv_pool* pool, const uint8_t* wire, uint64_t wire_bytes,
                       const uint64_t* msg_off, const uint32_t* msg_len, uint32_t n, uint64_t* ticket);
 int txv_ingest_admit(txv_ctx* ctx, uint64_t ticket, uint8_t* wire_status, uint8_t* pool_status);
+/* txv_ingest_decode with the messages' peer ids ("CheckTxWithInfo's senders" above): the column is
+ * copied before the call returns and used by the ticket's admit */
+int txv_ingest_decode_from(txv_ctx* ctx, txv_pool* pool, const uint8_t* wire, uint64_t wire_bytes,
+                           const uint64_t* msg_off, const uint32_t* msg_len, uint32_t n, const uint16_t* senders,
+                           uint64_t* ticket);
 /* txv_ingest_admit in its two halves, for a fourth stage (the admit thread waited for
  * each batch's pool statuses): txv_ingest_admit_submit hands the batch's CheckTx to the device (the
  * pool keeps its cache in HBM and the caps cannot bind: the decisions are enqueued behind the
