@@ -17,7 +17,6 @@
 // (batches of >= 768K votes) or V = 4 (configured); smaller batches run one vote per lane
 // (txv_k_scalarmult_points + txv_k_batch_encode, 4 waves/SIMD).
 #include <algorithm>
-#include <cstdlib>
 
 #include "ed25519_dev.h"
 #include "fe_inv_var.h"
@@ -26,12 +25,6 @@
 #include "walk_lds.h"
 
 using namespace txv;
-
-// K1a's SHA-512 may load block b+1's message words before compressing block b (measured equal:
-// K1a 298 vs 299-306 us at 116 vs 99 VGPRs, profiles/r01/k1a_prefetch; off)
-#ifndef TXV_K1A_PREFETCH
-#define TXV_K1A_PREFETCH 0
-#endif
 
 // K1b's shared inversion: the variable-time divstep inverse (fe_inv_var.h) or the Fermat
 // chain; the value is the same either way (encoding canonicalises)
@@ -136,11 +129,7 @@ __device__ __forceinline__ bool vote_challenge(const VerifyArgs& a, uint32_t i, 
   uint32_t dig[16];
   if constexpr (!FIELDS) {
     MsgView m{a.msg + i, a.n_pad, a.msg_words, a.msg_len[i]};
-#if TXV_K1A_PREFETCH
-    sha512_prefixed_pf(dig, pre, 8, m);
-#else
     sha512_prefixed(dig, pre, 8, m);
-#endif
   } else {
     // no message buffer: the blocks come from the vote's field columns (signbytes_dev.h).  The
     // builder is chosen per wave: the compile-time layout when every hashing lane has the same
@@ -166,70 +155,6 @@ __device__ __forceinline__ bool vote_challenge(const VerifyArgs& a, uint32_t i, 
   return true;
 }
 
-// the same out of line (the fused K1b: its SHA-512 registers then do not add to the walk's)
-__device__ __attribute__((noinline)) bool vote_challenge_call(const VerifyArgs& a, uint32_t i, uint32_t k_out[8],
-                                                              uint32_t s_out[8]) {
-  return vote_challenge(a, i, k_out, s_out);
-}
-
-// the scalar checks of vote i and its SHA-512 prefix (R || A as big-endian words); false when the
-// vote fails them (then no challenge is needed)
-__device__ __forceinline__ bool vote_checks(const VerifyArgs& a, uint32_t i, uint32_t s[16], uint64_t pre[8]) {
-  const uint8_t fl = a.flags[i];
-  const uint32_t v = a.val[i];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) s[j] = a.sig[(size_t)j * a.n_pad + i];
-  const bool bad = !(fl & TXV_FLAG_PENDING) || !(fl & TXV_FLAG_SIG64) || (fl & TXV_FLAG_BADMSG) ||
-                   (s[15] & 0xE0000000u) || !a.decode_ok[v] || !sc_lt_L(s + 8);
-  const uint32_t* pw = a.pubs_le + (size_t)v * 8;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    pre[j] = be64_from_le32(s[2 * j], s[2 * j + 1]);
-    pre[4 + j] = be64_from_le32(pw[2 * j], pw[2 * j + 1]);
-  }
-  return !bad;
-}
-
-// K1a with two votes per lane (TXV_K1A_PAIR=1, experiment): lane t takes votes t and t + n/2 and
-// runs their SHA-512 compressions interleaved (sha512_block2), so the dependent round chain of one
-// has the other's as independent work; 2 waves/SIMD at ~2x the VGPRs
-__global__ void __launch_bounds__(256, 2) txv_k_challenge2(VerifyArgs a) {
-  const uint32_t half = (a.n + 1) / 2;
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (a.k1a_zeroes_wctr && blockIdx.x == 0 && threadIdx.x < 8 * 16) a.wctr[threadIdx.x] = 0;
-  if (t >= half) return;
-  const uint32_t i0 = t, i1 = t + half;
-  const bool has1 = i1 < a.n;
-  uint32_t s0[16], s1[16];
-  uint64_t p0[8], p1[8];
-  const bool ok0 = vote_checks(a, i0, s0, p0);
-  const bool ok1 = has1 && vote_checks(a, has1 ? i1 : i0, s1, p1);
-  if (!ok0 && !ok1) {
-    a.ok_out[i0] = 0;
-    if (has1) a.ok_out[i1] = 0;
-    return;
-  }
-  const uint32_t j1 = has1 ? i1 : i0;
-  MsgView m0{a.msg + i0, a.n_pad, a.msg_words, a.msg_len[i0]};
-  MsgView m1{a.msg + j1, a.n_pad, a.msg_words, a.msg_len[j1]};
-  uint32_t d0[16], d1[16];
-  sha512_prefixed2(d0, p0, m0, d1, p1, m1, 8);
-  if (ok0) {
-    const sc k = sc_reduce512(d0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a.kbuf[(size_t)j * a.n_pad + i0] = k.v[j];
-  }
-  a.ok_out[i0] = ok0 ? 2 : 0;
-  if (has1) {
-    if (ok1) {
-      const sc k = sc_reduce512(d1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a.kbuf[(size_t)j * a.n_pad + i1] = k.v[j];
-    }
-    a.ok_out[i1] = ok1 ? 2 : 0;
-  }
-}
-
 // K1a: challenges of every pending vote into kbuf
 #ifndef TXV_K1A_WAVES
 #define TXV_K1A_WAVES 4
@@ -242,8 +167,6 @@ __global__ void __launch_bounds__(256, 2) txv_k_challenge2(VerifyArgs a) {
 template <bool FIELDS>
 __device__ __forceinline__ void challenge_body(const VerifyArgs& a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  // K1b's claim counters, when it follows on this stream (no launch of their own)
-  if (a.k1a_zeroes_wctr && blockIdx.x == 0 && threadIdx.x < 8 * 16) a.wctr[threadIdx.x] = 0;
   if (i >= a.n) return;
   if (!(a.flags[i] & TXV_FLAG_PENDING)) { a.ok_out[i] = 0; return; }   // K1b may walk every vote
   uint32_t k[8], s[8];
@@ -717,12 +640,7 @@ __global__ void __launch_bounds__(BLOCK, V == 8 ? 2 : TXV_V4_WAVES * BLOCK / 512
 #ifndef TXV_K1B_DYNAMIC
 #define TXV_K1B_DYNAMIC 1
 #endif
-// TXV_K1B_DYN_WAVES (experiment): waves per SIMD of the work-stealing K1b; 3 needs <= 168 VGPRs and
-// one 8 KiB entry buffer per wave (prefetch one addition ahead) to fit the 160 KiB of LDS
-#ifndef TXV_K1B_DYN_WAVES
-#define TXV_K1B_DYN_WAVES 2
-#endif
-template <int BLOCK, int WB, int WA, int V, int WAVES, bool FUSED>
+template <int BLOCK, int WB, int WA, int V>
 __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t n_chunks = (a.n_work + 63u) / 64u;
@@ -730,7 +648,7 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
   const uint32_t per = (n_chunks + xg - 1u) / xg;
   const uint32_t gwave = (blockIdx.x * BLOCK + threadIdx.x) >> 6;
   uint32_t* park = a.park + (size_t)gwave * V * TXV_PARK_WORDS * 64 + lane;
-  constexpr int PD = WAVES >= 3 ? 1 : 2;
+  constexpr int PD = 2;
   __shared__ uint4 pf[BLOCK / 64][PD * 8 * 64];
   uint4* wbuf = pf[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
   uint32_t src = 0;                      // ranges tried: (myx + src) % xg
@@ -757,24 +675,12 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
       if (c == 0xFFFFFFFFu) break;
       const uint32_t idx = 64u * c + lane;
       const uint32_t i = idx < a.n_work ? (a.order ? a.order[idx] : idx) : 0u;
-      bool on;
+      const bool on = idx < a.n_work && a.ok_out[i] == 2;
       uint32_t s[8], k[8];
-      if constexpr (FUSED) {
-        // K1a's work for this chunk here (arrival order, every vote of the batch): the SHA-512 of
-        // one wave interleaves with the other wave's walk on the SIMD
-        on = idx < a.n_work && (a.flags[i] & TXV_FLAG_PENDING) && vote_challenge_call(a, i, k, s);
-        if (idx < a.n_work && !on) a.ok_out[i] = 0;
-        if (!on) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { s[j] = 0u; k[j] = 0u; }
-        }
-      } else {
-        on = idx < a.n_work && a.ok_out[i] == 2;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          s[j] = on ? a.sig[(size_t)(8 + j) * a.n_pad + i] : 0u;
-          k[j] = on ? a.kbuf[(size_t)j * a.n_pad + i] : 0u;
-        }
+      for (int j = 0; j < 8; ++j) {
+        s[j] = on ? a.sig[(size_t)(8 + j) * a.n_pad + i] : 0u;
+        k[j] = on ? a.kbuf[(size_t)j * a.n_pad + i] : 0u;
       }
       // idle lanes walk the digit-0 (identity) entries of validator 0: the cooperative gathers
       // need every lane of the wave
@@ -827,19 +733,9 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
   }
 }
 
-template <int BLOCK, int WB, int WA, int V, int WAVES = 2>
-__global__ void __launch_bounds__(BLOCK, WAVES) TXV_K1B_VGPR_ATTR txv_k_scalarmult_dyn(VerifyArgs a) {
-  k1b_dyn_body<BLOCK, WB, WA, V, WAVES, false>(a);
-}
-// TXV_K1B_FUSED=1: K1a's work inside the chunks, capped at the unfused kernel's register budget so
-// the TxFlow kernels of the neighbouring batches still find VGPRs beside two K1b waves
-#ifndef TXV_K1B_FUSED_VGPRS
-#define TXV_K1B_FUSED_VGPRS 200
-#endif
-template <int BLOCK, int WB, int WA>
-__global__ void __launch_bounds__(BLOCK, 2) __attribute__((amdgpu_num_vgpr(TXV_K1B_FUSED_VGPRS)))
-txv_k_scalarmult_dyn_fused(VerifyArgs a) {
-  k1b_dyn_body<BLOCK, WB, WA, 8, 2, true>(a);
+template <int BLOCK, int WB, int WA, int V>
+__global__ void __launch_bounds__(BLOCK, 2) TXV_K1B_VGPR_ATTR txv_k_scalarmult_dyn(VerifyArgs a) {
+  k1b_dyn_body<BLOCK, WB, WA, V>(a);
 }
 
 // Split mode (lane_votes = 1): the inversion leaves the scalar-multiply kernel.  Under SIMD a
@@ -1291,10 +1187,6 @@ __global__ void txv_k_fe_selftest(const uint32_t* a, const uint32_t* b, uint32_t
 }
 
 // ---------------------------------------------------------------- host launchers
-extern "C" {
-
-}  // extern "C"
-
 template <int W>
 static void launch_build(const uint32_t* pubs_le, uint32_t n_points, uint32_t* tables, uint8_t* decode_ok,
                          uint32_t* addr_words, const uint32_t* out_slot, hipStream_t st) {
@@ -1308,14 +1200,8 @@ static void launch_build(const uint32_t* pubs_le, uint32_t n_points, uint32_t* t
 // K1c runs beside the other batches' kernels in a pipeline, so it need not fill the SIMDs itself:
 // at C5's 64k-vote batches G = 4 (256 waves) took K1b + K1c from 0.159-0.163 to 0.154 ms in the
 // pipeline and the latency to commit from 3.0-3.3 to 2.5-2.9 ms against G = 1 (one wave per SIMD)
-// (round 6, same boxes).  TXV_K1C_G overrides it (experiments)
+// (round 6, same boxes)
 static int k1c_votes_per_lane(uint32_t n_work) {
-  static const int forced = [] {
-    const char* e = getenv("TXV_K1C_G");
-    const int g = e ? atoi(e) : 0;
-    return (g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) ? g : 0;
-  }();
-  if (forced) return forced;
   for (int g : {32, 16, 8, 4, 2})
     if ((uint64_t)n_work >= (uint64_t)g * 64 * 256) return g;
   return 1;
@@ -1342,42 +1228,21 @@ static hipError_t launch_multi(const VerifyArgs* args, uint32_t grid, hipStream_
   if (args->lane_votes == 1) {
     if (!args->rpts) return hipErrorInvalidValue;
     if constexpr (WB >= 24) {
-      // TXV_K1B_SPLIT=0 (experiments): the one-vote-per-lane points kernel instead
-      static const bool split = !(getenv("TXV_K1B_SPLIT") && atoi(getenv("TXV_K1B_SPLIT")) == 0);
-      if (split) {
-        const uint32_t waves = (args->n_work + 15u) / 16u;
-        const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((waves + 3u) / 4u, std::max<uint32_t>(args->n_cus, 1u) * TXV_SPLIT_WAVES));
-        hipLaunchKernelGGL((txv_k_scalarmult_split<WB, WA>), dim3(blocks), dim3(256), 0, st, *args);
-        return launch_batch_encode(args, st);
-      }
+      const uint32_t waves = (args->n_work + 15u) / 16u;
+      const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((waves + 3u) / 4u, std::max<uint32_t>(args->n_cus, 1u) * TXV_SPLIT_WAVES));
+      hipLaunchKernelGGL((txv_k_scalarmult_split<WB, WA>), dim3(blocks), dim3(256), 0, st, *args);
+    } else {
+      hipLaunchKernelGGL((txv_k_scalarmult_points<B, WB, WA>), dim3(grid), dim3(B), 0, st, *args);
     }
-    hipLaunchKernelGGL((txv_k_scalarmult_points<B, WB, WA>), dim3(grid), dim3(B), 0, st, *args);
     return launch_batch_encode(args, st);
   } else if (args->lane_votes == 4) {
     hipLaunchKernelGGL((txv_k_scalarmult_multi<B, WB, WA, 4>), dim3(grid), dim3(B), 0, st, *args);
   } else if (args->lane_votes == 8) {
     if constexpr (WB >= 24) {
       if (TXV_K1B_DYNAMIC && args->wctr) {
-        if (!args->k1a_zeroes_wctr) {   // else K1a, the launch before this one on st, has zeroed them
-          const hipError_t e = hipMemsetAsync(args->wctr, 0, 8 * 16 * sizeof(uint32_t), st);
-          if (e != hipSuccess) return e;
-        }
-        if constexpr (TXV_K1B_DYN_WAVES >= 3) {
-          // persistent: every resident slot (256-thread blocks, TXV_K1B_DYN_WAVES per SIMD)
-          // TXV_K1B_DYN_BLOCKS = blocks per CU x 100 (default: every slot); fewer leave SIMDs with
-          // room for the neighbouring batches' TxFlow kernels
-          // (grid capped at the park buffer's capacity: one V-slot park per wave)
-          static const int per100 = getenv("TXV_K1B_DYN_BLOCKS") ? atoi(getenv("TXV_K1B_DYN_BLOCKS")) : 100 * TXV_K1B_DYN_WAVES;
-          const uint32_t want = std::max<uint32_t>(8, args->n_cus * (uint32_t)std::max(per100, 1) / 100u);
-          const uint32_t grid3 = std::min<uint32_t>(want, args->park_waves / 4u);
-          if (!grid3) return hipErrorInvalidValue;
-          hipLaunchKernelGGL((txv_k_scalarmult_dyn<256, WB, WA, 8, TXV_K1B_DYN_WAVES>),
-                             dim3(grid3), dim3(256), 0, st, *args);
-        } else if (args->fused_k1a) {
-          hipLaunchKernelGGL((txv_k_scalarmult_dyn_fused<B, WB, WA>), dim3(grid), dim3(B), 0, st, *args);
-        } else {
-          hipLaunchKernelGGL((txv_k_scalarmult_dyn<B, WB, WA, 8>), dim3(grid), dim3(B), 0, st, *args);
-        }
+        const hipError_t e = hipMemsetAsync(args->wctr, 0, 8 * 16 * sizeof(uint32_t), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((txv_k_scalarmult_dyn<B, WB, WA, 8>), dim3(grid), dim3(B), 0, st, *args);
       } else {
         hipLaunchKernelGGL((txv_k_scalarmult_multi<B, WB, WA, 8>), dim3(grid), dim3(B), 0, st, *args);
       }
@@ -1431,21 +1296,13 @@ bool txv_verify_windows_supported(int wb, int wa) {
   return wa == 16 && (wb == 20 || wb == 22);
 }
 
-bool txv_k1b_fusable(int wb, const VerifyArgs* args) {
-  return TXV_K1B_DYNAMIC && TXV_K1B_DYN_WAVES < 3 && wb >= 24 && args->lane_votes == 8 && args->wctr && !args->order;
-}
-
-// K1a alone (the AddVote pipeline runs it on another stream than K1b, beside the previous
-// batch's K1b: K1b leaves ~116 VGPRs per SIMD free, room for one K1a wave)
+// K1a alone: from the field columns when there is no message buffer (args->msg == null), else
+// from the buffer
 hipError_t txv_launch_challenge(const VerifyArgs* args, hipStream_t st) {
   if (!args->n) return hipSuccess;
-  static const bool pair = getenv("TXV_K1A_PAIR") && atoi(getenv("TXV_K1A_PAIR")) == 1;
-  if (!args->msg) {   // (the paired experiment reads the message buffer)
+  if (!args->msg) {
     if (!args->chain_field || !args->chain_field_len) return hipErrorInvalidValue;
     hipLaunchKernelGGL(txv_k_challenge_fields, dim3((args->n + 255) / 256), dim3(256), 0, st, *args);
-  } else if (pair) {
-    const uint32_t half = (args->n + 1) / 2;
-    hipLaunchKernelGGL(txv_k_challenge2, dim3((half + 255) / 256), dim3(256), 0, st, *args);
   } else {
     hipLaunchKernelGGL(txv_k_challenge, dim3((args->n + 255) / 256), dim3(256), 0, st, *args);
   }

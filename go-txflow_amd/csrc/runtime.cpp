@@ -57,25 +57,6 @@ constexpr uint32_t kTableWords4 = 64 * 9 * 32;
 inline bool valid_window(int w) {
   return w == 4 || w == 8 || w == 10 || w == 12 || w == 14 || w == 16 || w == 18 || w == 20 || w == 21;
 }
-// TXV_K1A_ON_KEY_STREAM=1 runs K1a on the key stream, beside the previous batch's K1b (its 99
-// VGPRs do not fit beside two K1b waves, so it mostly fills K1b's tail): measured 614-621 vs
-// 608M votes/s (within box noise, profiles/r02/ab), while the two kernels' overlapping durations
-// no longer add up to the verify time; off: K1a then K1b on the verify stream
-#ifndef TXV_K1A_ON_KEY_STREAM
-#define TXV_K1A_ON_KEY_STREAM 0
-#endif
-// TXV_K1A_FIELDS=1: run_slot launches no txv_k_signbytes; K1a builds R || A || SignBytes in
-// registers from the field columns (signbytes_dev.h).  0: the SignBytes go through the slot's
-// message buffer (one launch, one write and one read of msg_words x n_pad words per batch)
-#ifndef TXV_K1A_FIELDS
-#define TXV_K1A_FIELDS 1
-#endif
-// TXV_K1A_WCTR=1 (experiment): K1a zeroes K1b's claim counters when it runs just before K1b on the
-// verify stream (not on the key stream, not fused) instead of a hipMemsetAsync between the two.
-// No gain that could be told from the runs' spread (measured dead ends): off
-#ifndef TXV_K1A_WCTR
-#define TXV_K1A_WCTR 0
-#endif
 constexpr uint32_t kStagedSlots = 4;   // 0-3 staged (0-2 also the submit ring)
 constexpr uint32_t kSubmitRing = 4;    // txv_submit_votes batches in flight
 constexpr uint32_t kVcodeEmpty = TXV_VCODE_EMPTY, kVcodeUnknown = TXV_VCODE_UNKNOWN;   // txv_flow.h
@@ -143,9 +124,9 @@ struct Slot {
   uint8_t* h_out = nullptr; uint8_t* m_out = nullptr;
   FlowEvent* h_ev = nullptr; FlowEvent* m_ev = nullptr;
   FlowSummary* h_sum = nullptr; FlowSummary* m_sum = nullptr;
-  // copy stream: 3 upload done; key stream: 0 prep start, 8 prep + SignBytes done (K1a starts),
-  // 1 K1a done; verify stream: 7 K1b start, 2 verify done; flow stream: 4 results in host memory
-  // (+ commit sink), 5 tallied, 6 set keying done
+  // copy stream: 3 upload done; key stream: 0 prep start, 1 prep done; verify stream: 7 K1a start,
+  // 8 K1a done (K1b starts), 2 verify done; flow stream: 4 results in host memory (+ commit sink),
+  // 5 tallied, 6 set keying done
   hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool launched = false;           // a chain was enqueued on this slot (its ev[4] marks the end)
   uint32_t* sink = nullptr;        // txv_set_commit_sink: packed commit state after each batch of this slot
@@ -206,11 +187,7 @@ struct txv_ctx {
   hipStream_t stream = nullptr;        // flow: TxFlow keying + tally kernels, resets, readers (batch order)
   hipStream_t vstream = nullptr;       // verify: prep + K1a/K1b (batch k+1 verifies while batch k tallies)
   hipStream_t copy_stream = nullptr;   // batch uploads, so batch k+1's H2D overlaps batch k's kernels
-  hipStream_t key_stream = nullptr;    // txv_sig_keys (pool ingest), wire decode, and each batch's prep + SignBytes
-  hipEvent_t tally_ev = nullptr;        // TXV_K1B_AFTER_TALLY: the newest batch's tally end (flow stream)
-  bool tally_ev_set = false;
-  hipEvent_t vend_ev[4] = {};           // TXV_PREP_AFTER_K1B: the last batches' K1b ends (verify stream)
-  uint64_t vend_n = 0;
+  hipStream_t key_stream = nullptr;    // txv_sig_keys (pool ingest), wire decode, and each batch's prep
   uint64_t next_ticket = 1;            // txv_submit_votes ring over slots 0 .. kSubmitRing - 1
   ErrMsg err;
   std::mutex mu;
@@ -771,7 +748,6 @@ VerifyArgs verify_args(txv_ctx* c, Slot& s, const uint32_t* pubs, const uint8_t*
   a.ok_out = s.d_ok;
   a.tslot = tslot;
   a.park = c->d_park;
-  a.park_waves = (uint32_t)(c->park_words / ((size_t)8 * TXV_PARK_WORDS * 64));
   a.n_cus = (uint32_t)c->n_cus;
   a.wctr = c->d_wctr;
   a.rpts = s.d_rpts;
@@ -1127,19 +1103,11 @@ FlowBatch flow_batch(const txv_ctx* c, const Slot& s) {
   return b;
 }
 
-// device times of a slot's last run (its events have completed): prep (+ SignBytes), verify,
+// device times of a slot's last run (its events have completed): prep, verify (K1a + K1b),
 // tally after verify, and the whole chain from the prep's start
 int slot_kernel_ms(txv_ctx* c, Slot& s, float* ms) {
-  // prep + SignBytes; K1a + K1b (each on its own stream: their durations added)
-  float k1a = 0.f, k1b = 0.f;
-  if (TXV_K1A_ON_KEY_STREAM) {
-    HIP_TRY(c, hipEventElapsedTime(&ms[0], s.ev[0], s.ev[8]));
-    HIP_TRY(c, hipEventElapsedTime(&k1a, s.ev[8], s.ev[1]));
-  } else {
-    HIP_TRY(c, hipEventElapsedTime(&ms[0], s.ev[0], s.ev[1]));
-  }
-  HIP_TRY(c, hipEventElapsedTime(&k1b, s.ev[7], s.ev[2]));
-  ms[1] = k1a + k1b;
+  HIP_TRY(c, hipEventElapsedTime(&ms[0], s.ev[0], s.ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&ms[1], s.ev[7], s.ev[2]));
   HIP_TRY(c, hipEventElapsedTime(&ms[2], s.ev[2], s.ev[5]));
   HIP_TRY(c, hipEventElapsedTime(&ms[3], s.ev[0], s.ev[5]));
   return TXV_OK;
@@ -1169,7 +1137,7 @@ GossipSink gossip_sink(const txv_ctx* c, const Slot& s) {
   return k;
 }
 
-// the whole AddVote chain of a staged batch: prep + SignBytes -> K1a/K1b verify (verify
+// the whole AddVote chain of a staged batch: prep (key stream) -> K1a/K1b verify (verify
 // stream), set keying -> new ids -> tally -> results into mapped host memory (flow stream)
 int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   Slot& s = c->slots[slot];
@@ -1205,9 +1173,9 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   // Three compute queues, so that batch k+1 verifies while batch k tallies and nothing but
   // K1a/K1b sits on the verify stream:
   //   key stream   (after the uploads on the copy stream) prep (pre-checks, validator lookup,
-  //                signature transpose) and SignBytes: they read only the uploaded columns and
-  //                run beside the previous batch's K1b; the copy stream stays pure DMA, so batch
-  //                k+2's upload never queues behind them
+  //                signature transpose): it reads only the uploaded columns and runs beside the
+  //                previous batch's K1b; the copy stream stays pure DMA, so batch k+2's upload
+  //                never queues behind it
   //   vstream      K1a/K1b: reads nothing the TxFlow owns, so it never waits for an earlier
   //                batch's tally
   //   flow stream  set keying + new set ids, then -- after this batch's verify -- the tally:
@@ -1223,60 +1191,26 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     HIP_TRY(c, hipEventRecord(s.ev[3], ps));
   }
   HIP_TRY(c, hipStreamWaitEvent(c->stream, s.ev[3], 0));
-  // TXV_PREP_AFTER_K1B=1 (experiment): this batch's prep + SignBytes wait for the K1b two batches
-  // back, so they run beside the next K1a instead of beside a K1b
-  static const bool prep_after = getenv("TXV_PREP_AFTER_K1B") && atoi(getenv("TXV_PREP_AFTER_K1B")) == 1;
-  if (prep_after && c->vend_n >= 2) HIP_TRY(c, hipStreamWaitEvent(ps, c->vend_ev[(c->vend_n - 2) % 4], 0));
   HIP_TRY(c, hipEventRecord(s.ev[0], ps));
-  SignBytesArgs sa{};
-  sa.n = s.n; sa.n_pad = s.n_pad; sa.msg_words = s.msg_words; sa.chain_len = fb.chain_len;
-  sa.height = s.d_fh; sa.ts_sec = s.d_fs; sa.ts_nanos = s.d_fn; sa.txhash_off = s.d_fo; sa.txhash_len = s.d_fl;
-  sa.txhash = s.d_arena_th; sa.chain = c->d_chain; sa.msg_len = nullptr; sa.nil = s.has_nil ? s.d_nil : nullptr;
-  sa.msg = s.d_msg;
   VerifyArgs va = verify_args(c, s, c->d_pubs, c->d_decode_ok, c->d_atables, c->tab_w, c->d_vslot);
   va.order = nullptr;          // arrival order; K1a marks the non-pending votes
   va.n_work = s.n;
   va.lane_votes = launch_lane_votes(c, c->b_w, va.n_work);
   if (!txv_verify_windows_supported(c->b_w, c->tab_w)) { c->err = "verify windows"; return TXV_EDEVICE; }
-  // TXV_K1B_FUSED=1 (experiment): the work-stealing K1b computes each chunk's challenges itself
-  static const bool fuse = getenv("TXV_K1B_FUSED") && atoi(getenv("TXV_K1B_FUSED")) == 1;
-  va.fused_k1a = fuse && txv_k1b_fusable(c->b_w, &va) ? 1u : 0u;
-  // no message buffer: K1a reads the field columns itself (the fused K1b experiment reads the buffer)
-  const bool k1a_fields = TXV_K1A_FIELDS && !va.fused_k1a;
-  if (k1a_fields) {
-    if (!c->d_chain_field && (r = upload_chain_field(c))) return r;
-    va.msg = nullptr;
-    va.height = sa.height; va.ts_sec = sa.ts_sec; va.ts_nanos = sa.ts_nanos;
-    va.txhash_off = sa.txhash_off; va.txhash_len = sa.txhash_len; va.txhash = sa.txhash;
-    va.chain_field = c->d_chain_field + txv::kChainFieldPad; va.chain_field_len = c->chain_field_len;
-  }
-  // TXV_K1A_WCTR: K1a, then K1b on the verify stream: K1a's first block zeroes K1b's claim counters
-  va.k1a_zeroes_wctr = TXV_K1A_WCTR && !TXV_K1A_ON_KEY_STREAM && !va.fused_k1a && va.wctr ? 1u : 0u;
+  // no message buffer: K1a reads the field columns itself
+  if (!c->d_chain_field && (r = upload_chain_field(c))) return r;
+  va.msg = nullptr;
+  va.height = s.d_fh; va.ts_sec = s.d_fs; va.ts_nanos = s.d_fn;
+  va.txhash_off = s.d_fo; va.txhash_len = s.d_fl; va.txhash = s.d_arena_th;
+  va.chain_field = c->d_chain_field + txv::kChainFieldPad; va.chain_field_len = c->chain_field_len;
   HIP_TRY(c, txv_flow_prep(&fs, &fb, ps));
-  if (!k1a_fields) HIP_TRY(c, txv_launch_signbytes(&sa, ps));
-  if (TXV_K1A_ON_KEY_STREAM && !va.fused_k1a) {
-    HIP_TRY(c, hipEventRecord(s.ev[8], ps));
-    HIP_TRY(c, txv_launch_challenge(&va, ps));
-  }
   HIP_TRY(c, hipEventRecord(s.ev[1], ps));
   HIP_TRY(c, hipStreamWaitEvent(c->vstream, s.ev[1], 0));
   HIP_TRY(c, hipEventRecord(s.ev[7], c->vstream));
-  // TXV_K1B_AFTER_TALLY=1 (experiment): K1b waits for the previous batch's tally, which then runs
-  // beside this batch's K1a instead of beside its K1b
-  static const bool after_tally = getenv("TXV_K1B_AFTER_TALLY") && atoi(getenv("TXV_K1B_AFTER_TALLY")) == 1;
-  if (!TXV_K1A_ON_KEY_STREAM || va.fused_k1a) {
-    if (!va.fused_k1a) HIP_TRY(c, txv_launch_challenge(&va, c->vstream));
-    if (after_tally && c->tally_ev_set) HIP_TRY(c, hipStreamWaitEvent(c->vstream, c->tally_ev, 0));
-    HIP_TRY(c, hipEventRecord(s.ev[8], c->vstream));   // K1a | K1b split (txv_slot_verify_ms)
-  }
+  HIP_TRY(c, txv_launch_challenge(&va, c->vstream));
+  HIP_TRY(c, hipEventRecord(s.ev[8], c->vstream));   // K1a | K1b split (txv_slot_verify_ms)
   HIP_TRY(c, txv_launch_scalarmult(c->b_w, c->tab_w, &va, verify_grid(c, s.n), c->vstream));
   HIP_TRY(c, hipEventRecord(s.ev[2], c->vstream));
-  if (prep_after) {
-    hipEvent_t& ve = c->vend_ev[c->vend_n % 4];
-    if (!ve) HIP_TRY(c, hipEventCreateWithFlags(&ve, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(ve, c->vstream));
-    ++c->vend_n;
-  }
   HIP_TRY(c, txv_flow_route(&fs, &fb, c->stream));
   HIP_TRY(c, txv_flow_new_ids(&fs, &fb, c->stream));
   HIP_TRY(c, hipEventRecord(s.ev[6], c->stream));
@@ -1298,11 +1232,6 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   HIP_TRY(c, hipStreamWaitEvent(c->stream, s.ev[2], 0));
   HIP_TRY(c, txv_flow_tally(&fs, &fb, sets_bound, c->stream));
   HIP_TRY(c, hipEventRecord(s.ev[5], c->stream));
-  if (after_tally) {
-    if (!c->tally_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->tally_ev, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->tally_ev, c->stream));
-    c->tally_ev_set = true;
-  }
   if (s.sink) HIP_TRY(c, txv_flow_pack(&fs, s.sink, (s.sink_cap + 31) / 32, s.sink_cap, c->stream));
   // txv_update_sink_enable: the batch's Update list (registries the builder ranks in LDS; a larger
   // one leaves the slot without a list, which txv_update_list reports)
@@ -2775,13 +2704,8 @@ int txv_slot_verify_ms(txv_ctx* c, uint32_t slot, float* ms2) {
   Slot& s = c->slots[slot];
   if (!s.launched) { c->err = "slot never ran"; return TXV_ESTATE; }
   HIP_TRY(c, hipEventSynchronize(s.ev[4]));
-  if (TXV_K1A_ON_KEY_STREAM) {
-    HIP_TRY(c, hipEventElapsedTime(&ms2[0], s.ev[8], s.ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms2[1], s.ev[7], s.ev[2]));
-  } else {
-    HIP_TRY(c, hipEventElapsedTime(&ms2[0], s.ev[7], s.ev[8]));
-    HIP_TRY(c, hipEventElapsedTime(&ms2[1], s.ev[8], s.ev[2]));
-  }
+  HIP_TRY(c, hipEventElapsedTime(&ms2[0], s.ev[7], s.ev[8]));
+  HIP_TRY(c, hipEventElapsedTime(&ms2[1], s.ev[8], s.ev[2]));
   return TXV_OK;
 }
 
@@ -3444,7 +3368,7 @@ int txv_sig_keys_overlap(txv_ctx* c, const txv_votes* v, const uint8_t* sig_full
     PK_TRY(hipMemcpyAsync(c->h_pk_keys + (size_t)c0 * 8, c->d_pk_keys + (size_t)c0 * 8, (size_t)(c1 - c0) * 32,
                               hipMemcpyDeviceToHost, c->key_stream));
   }
-  // the wait below is for this event, not the stream: a batch's prep / SignBytes that another
+  // the wait below is for this event, not the stream: a batch's prep that another
   // thread's txv_submit_votes enqueues on the key stream after these keys is not waited for
   // (work enqueued before them still is: the stream is in order)
   PK_TRY(hipEventRecord(c->pk_ev, c->key_stream));

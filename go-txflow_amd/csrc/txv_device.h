@@ -40,9 +40,7 @@ struct VerifyArgs {
                                // then the exclusive prefix product of the lane's Z (K1b -> K1c)
   uint32_t* wctr;              // [8 * 16] chunk counters of the work-stealing K1b (one per XCD
                                // range, 64 B apart), zeroed before each launch
-  uint32_t park_waves;         // waves the park buffer holds (V = 8 slots each): caps persistent grids
   uint32_t n_cus;              // CUs of the context's device
-  uint32_t fused_k1a;          // TXV_K1B_FUSED: the work-stealing K1b computes the challenges itself (no K1a)
   const uint32_t* tslot;       // [n_vals] table slot of each validator in atables, or null (slot = index)
   // msg == null: K1a builds R || A || SignBytes in registers from the TxVote field columns
   // (signbytes_dev.h) and reads no message buffer; msg_words and msg_len are then unused
@@ -54,7 +52,6 @@ struct VerifyArgs {
   const uint8_t* txhash;       // TxHash arena (>= 16 bytes of padding behind it)
   const uint8_t* chain_field;  // [0x2a uvarint(len) ChainID] 0x80, kChainFieldPad zero bytes around it
   uint32_t chain_field_len;    // with the 0x80
-  uint32_t k1a_zeroes_wctr;    // K1a precedes K1b on its stream and zeroes wctr: K1b's launch skips the memset
 };
 
 #define TXV_PARK_WORDS 33          // X, Y, prefix product, Z of one parked vote; its vote index + 1
@@ -179,7 +176,6 @@ hipError_t txv_launch_base_encode(uint32_t* rpts, uint32_t n, uint32_t n_pad, ui
 hipError_t txv_launch_sign_finish(const SignTxArgs* args, hipStream_t st);
 hipError_t txv_launch_valu_probe(int op, uint32_t* out, uint32_t blocks, int iters, hipStream_t st);
 hipError_t txv_launch_signbytes(const SignBytesArgs* args, hipStream_t st);
-bool txv_k1b_fusable(int wb, const VerifyArgs* args);   // the launch takes the work-stealing K1b
 hipError_t txv_launch_nil_from_status(const uint8_t* st, uint32_t n, uint8_t* nil, uint32_t or_nil, hipStream_t s);
 hipError_t txv_launch_sig_keys(const uint32_t* sig, const uint32_t* sig_len, uint32_t n, uint32_t* keys,
                                 hipStream_t st);

@@ -146,7 +146,7 @@ def test_changed_votes_nil_entries_and_short_signatures(gpu_ctx, oracle_lib, n):
 
 def test_two_staged_slots_back_to_back(gpu_ctx, oracle_lib):
     """two runs queued without a wait between them give what each gives alone: K1b's claim counters
-    start from zero in both, whether the memset or (TXV_K1A_WCTR=1) the K1a before it clears them"""
+    start from zero in both"""
     import txflow_amd as T
     _, pubs, va = _signed(gpu_ctx, "mixed", 200)
     _, _, vb = _signed(gpu_ctx, "u64", 65)
