@@ -132,31 +132,122 @@ struct Slot {
   uint32_t* sink = nullptr;        // txv_set_commit_sink: packed commit state after each batch of this slot
   uint32_t sink_cap = 0;
   uint64_t ticket = 0;    // txv_submit_votes ticket in flight on this slot (0 = none)
-  // txv_update_sink_enable (submit ring slots): the batch's Update list, built behind its tally
-  // (kernels_update.hip): signatures [cap][16], lengths, TxVote.Size(), set ids; the result words
-  // (entries, fired sets, entries needed, overflow) in mapped host memory
-  uint32_t *u_sig = nullptr, *u_len = nullptr, *u_size = nullptr, *u_set = nullptr;
-  uint32_t *h_ures = nullptr, *m_ures = nullptr;
-  bool u_built = false;            // the slot's last chain built a list
-  uint64_t u_ticket = 0;           // the ticket that chain belongs to (0: none, e.g. a staged run)
-  hipEvent_t u_cons_ev = nullptr;  // a pool's device-to-device staging of the list (pooldev_stage_dev) has
-  bool u_cons = false;             // ended: the slot's next list build waits for it
-  // txv_store_sink_enable (submit ring slots): the batch's SaveTx records, encoded behind its tally
-  // (kernels_store.hip): the byte buffer in HBM; the records' offsets, part lengths and set ids, and the
-  // result words (StoreSink::result) in mapped host memory.  u_ticket names the batch for both sinks
-  uint8_t* st_buf = nullptr;
-  StoreRec *h_strec = nullptr, *m_strec = nullptr;
-  uint32_t *h_stres = nullptr, *m_stres = nullptr;
-  bool st_built = false;           // the slot's last chain built records
-  uint32_t st_reading = 0;         // txv_store_records calls copying out of st_buf with no lock held
-  // txv_gossip_sink_enable (submit ring slots): the batch's TxVoteMessages, encoded from its raw columns
-  // before its tally (kernels_gossip.hip): bytes and descriptors in HBM, the result words
-  // (GossipSink::result) in mapped host memory, and the read-out's pinned copy of the descriptors
-  uint8_t* g_buf = nullptr;
-  GossipDesc *g_desc = nullptr, *h_gdesc = nullptr;
-  uint32_t *h_gres = nullptr, *m_gres = nullptr;
-  bool g_built = false;            // the slot's last chain built messages
-  uint32_t g_reading = 0;          // a txv_gossip_msgs call is copying out of g_buf / g_desc with no lock held
+  uint64_t sink_ticket = 0;        // the ticket the slot's last chain belongs to, for the sinks (0: none, e.g. a staged run)
+};
+
+template <typename T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+template <typename T> void hfree(T*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } }
+
+// The three per-batch products that stay in HBM.  Each sink owns its capacities (0 = off), the builder's
+// scratch -- shared by the slots: the builders run one after another on the flow stream -- and the
+// state of the submit ring's slots, which alone can hold a product.
+// txv_update_sink_enable: the batch's Update list, built behind its tally (kernels_update.hip)
+struct UpdateSinkState {
+  uint32_t upd_cap = 0;            // entries per slot
+  uint64_t *d_cnt = nullptr, *d_blk = nullptr;   // the list builder's scratch (UpdateSink, txv_flow.h)
+  uint32_t *d_sid = nullptr, *d_fired = nullptr;
+  uint32_t* d_keys = nullptr;      // [upd_cap][8] the list's keys (txv_pool_update_fired on a host-cache pool)
+  struct PerSlot {
+    // signatures [cap][16], lengths, TxVote.Size(), set ids; the result words (entries, fired sets,
+    // entries needed, overflow) in mapped host memory
+    uint32_t *sig = nullptr, *len = nullptr, *size = nullptr, *set = nullptr;
+    uint32_t *h_res = nullptr, *m_res = nullptr;
+    bool built = false;            // the slot's last chain built a list
+    hipEvent_t cons_ev = nullptr;  // a pool's device-to-device staging of the list (pooldev_stage_dev) has
+    bool cons = false;             // ended: the slot's next list build waits for it
+  } slot[kSubmitRing];
+  UpdateSink args(uint32_t k) const {
+    const PerSlot& s = slot[k];
+    UpdateSink u{};
+    u.cap = upd_cap; u.sig = s.sig; u.len = s.len; u.size = s.size; u.set = s.set; u.result = s.m_res;
+    u.cnt = d_cnt; u.sid = d_sid; u.blk = d_blk; u.fired = d_fired;
+    return u;
+  }
+  // the list's columns are tagged with the stamp: cleared where the stamp starts over
+  hipError_t clear_tags(uint32_t max_batch, hipStream_t st) {
+    return d_cnt ? hipMemsetAsync(d_cnt, 0, (size_t)max_batch * sizeof(uint64_t), st) : hipSuccess;
+  }
+  void free() {
+    for (PerSlot& s : slot) {
+      dfree(s.sig); dfree(s.len); dfree(s.size); dfree(s.set); hfree(s.h_res);
+      if (s.cons_ev) (void)hipEventDestroy(s.cons_ev);
+    }
+    dfree(d_cnt); dfree(d_blk); dfree(d_sid); dfree(d_fired); dfree(d_keys);
+  }
+};
+
+// txv_store_sink_enable: the batch's SaveTx records, encoded behind its tally (kernels_store.hip)
+struct StoreSinkState {
+  uint64_t st_bytes = 0;           // bytes and records per slot
+  uint32_t st_recs = 0;
+  uint64_t *d_tag = nullptr, *d_rlen = nullptr, *d_blk = nullptr, *d_foff = nullptr;   // the record builder's
+  uint32_t* d_fired = nullptr;                                                         // scratch (StoreSink)
+  hipStream_t stream = nullptr;    // txv_store_records' copies: off the flow and verify streams
+  struct PerSlot {
+    // the byte buffer in HBM; the records' offsets, part lengths and set ids, and the result words
+    // (StoreSink::result) in mapped host memory
+    uint8_t* buf = nullptr;
+    StoreRec *h_rec = nullptr, *m_rec = nullptr;
+    uint32_t *h_res = nullptr, *m_res = nullptr;
+    bool built = false;            // the slot's last chain built records
+    uint32_t reading = 0;          // txv_store_records calls copying out of buf with no lock held
+  } slot[kSubmitRing];
+  StoreSink args(uint32_t k) const {
+    const PerSlot& s = slot[k];
+    StoreSink a{};
+    a.cap_bytes = st_bytes; a.cap_recs = st_recs;
+    a.buf = s.buf; a.rec = s.m_rec; a.result = s.m_res;
+    a.tag = d_tag; a.rlen = d_rlen; a.blk = d_blk; a.fired = d_fired; a.foff = d_foff;
+    return a;
+  }
+  // the records' tags carry the stamp, as the Update list's columns do
+  hipError_t clear_tags(uint32_t max_batch, hipStream_t st) {
+    return d_tag ? hipMemsetAsync(d_tag, 0, (size_t)max_batch * sizeof(uint64_t), st) : hipSuccess;
+  }
+  void free() {
+    for (PerSlot& s : slot) { dfree(s.buf); hfree(s.h_rec); hfree(s.h_res); }
+    dfree(d_tag); dfree(d_rlen); dfree(d_blk); dfree(d_fired); dfree(d_foff);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// txv_gossip_sink_enable: the batch's TxVoteMessages, encoded from its raw columns before its tally
+// (kernels_gossip.hip).  Every scratch word a batch reads it wrote itself: nothing is tagged
+struct GossipSinkState {
+  uint64_t g_bytes = 0;            // bytes and entries per slot
+  uint32_t g_msgs = 0, g_prefix = 0;   // ... and the TxVoteMessage amino prefix
+  uint64_t *d_ent = nullptr, *d_lay = nullptr, *d_blk = nullptr;   // the chain's scratch (GossipSink)
+  hipStream_t stream = nullptr;    // txv_gossip_msgs' copies
+  struct PerSlot {
+    // bytes and descriptors in HBM, the result words (GossipSink::result) in mapped host memory, and
+    // the read-out's pinned copy of the descriptors
+    uint8_t* buf = nullptr;
+    GossipDesc *desc = nullptr, *h_desc = nullptr;
+    uint32_t *h_res = nullptr, *m_res = nullptr;
+    bool built = false;            // the slot's last chain built messages
+    uint32_t reading = 0;          // a txv_gossip_msgs call is copying out of buf / desc with no lock held
+  } slot[kSubmitRing];
+  GossipSink args(uint32_t k) const {
+    const PerSlot& s = slot[k];
+    GossipSink a{};
+    a.cap_bytes = g_bytes; a.cap_msgs = g_msgs; a.prefix = g_prefix;
+    a.buf = s.buf; a.desc = s.desc; a.result = s.m_res;
+    a.ent = d_ent; a.lay = d_lay; a.blk = d_blk;
+    return a;
+  }
+  void free() {
+    for (PerSlot& s : slot) { dfree(s.buf); dfree(s.desc); hfree(s.h_desc); hfree(s.h_res); }
+    dfree(d_ent); dfree(d_lay); dfree(d_blk);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// What the route and the sign ring's entries share: ticket t runs on entry (t - 1) % ring length; an
+// entry is free again once its ticket was waited for.  Guarded by txv_ctx::mu
+struct RingHead {
+  uint64_t ticket = 0;             // the chain in flight on this entry (0 = free)
+  bool waiting = false;            // a wait for it is in its event wait
+  hipEvent_t ev = nullptr;         // behind the chain's last kernel
 };
 
 }  // namespace
@@ -266,25 +357,9 @@ struct txv_ctx {
   uint64_t sets_seq = 0;            // run_seq n_sets_host belongs to (older summaries are not applied)
   uint64_t unfetched = 0;           // votes of batches run but not fetched yet (each may add sets)
   uint32_t poisoned = 0;            // TXV_FERR_* seen: every AddVote call fails until txv_reset_flow
-  // txv_update_sink_enable: entries per slot (0 = off) and the list builder's scratch (UpdateSink,
-  // txv_flow.h), shared by the slots: the builders run one after another on the flow stream
-  uint32_t upd_cap = 0;
-  uint64_t *d_upd_cnt = nullptr, *d_upd_blk = nullptr;
-  uint32_t *d_upd_sid = nullptr, *d_upd_fired = nullptr;
-  uint32_t* d_upd_keys = nullptr;   // [upd_cap][8] the list's keys (txv_pool_update_fired on a host-cache pool)
-  // txv_store_sink_enable: bytes and records per slot (0 = off), the record builder's scratch
-  // (StoreSink, txv_flow.h), shared by the slots as the Update list's is, and the read-out's stream
-  uint64_t st_bytes = 0;
-  uint32_t st_recs = 0;
-  uint64_t *d_st_tag = nullptr, *d_st_rlen = nullptr, *d_st_blk = nullptr, *d_st_foff = nullptr;
-  uint32_t* d_st_fired = nullptr;
-  hipStream_t store_stream = nullptr;   // txv_store_records' copies: off the flow and verify streams
-  // txv_gossip_sink_enable: bytes and entries per slot (0 = off), the TxVoteMessage amino prefix, the
-  // chain's scratch (GossipSink, txv_flow.h), shared by the slots, and the read-out's stream
-  uint64_t g_bytes = 0;
-  uint32_t g_msgs = 0, g_prefix = 0;
-  uint64_t *d_g_ent = nullptr, *d_g_lay = nullptr, *d_g_blk = nullptr;
-  hipStream_t gossip_stream = nullptr;  // txv_gossip_msgs' copies
+  UpdateSinkState upd;             // the batch sinks of the submit ring's slots
+  StoreSinkState store;
+  GossipSinkState gossip;
   // caller memory registered with txv_host_register (DMA'd without a staging copy)
   std::vector<std::pair<uintptr_t, uint64_t>> registered;
   std::mutex reg_mu;               // `registered` is changed under mu and reg_mu: read under either (the
@@ -301,9 +376,7 @@ struct txv_ctx {
   // timestamps (grown as ensure_slot grows a slot's), the chain's scratch, the event behind its
   // uploads (copy stream) and the events around its kernels (key stream).  sign_mu serialises the
   // submits; the entries are guarded by mu
-  struct SignEntry {
-    uint64_t ticket = 0;               // the chain in flight on this entry (0 = free)
-    bool waiting = false;              // a txv_sign_txs_wait is in its event wait
+  struct SignEntry : RingHead {
     uint32_t n_cap = 0, mw_cap = 0;
     uint64_t tx_cap = 0;
     uint8_t *h_tx = nullptr, *d_tx = nullptr;
@@ -313,7 +386,7 @@ struct txv_ctx {
     int32_t *h_nanos = nullptr, *d_nanos = nullptr;
     uint64_t* d_msg = nullptr;
     uint32_t *d_msg_len = nullptr, *d_r = nullptr, *d_rpts = nullptr, *d_renc = nullptr;
-    hipEvent_t up_ev = nullptr, ev0 = nullptr, ev = nullptr;
+    hipEvent_t up_ev = nullptr, ev0 = nullptr;
     txv_route_meta meta{};
   } sign[TXV_SIGN_RING];
   std::mutex sign_mu;
@@ -327,9 +400,7 @@ struct txv_ctx {
   // ticket's memset of maxhl would race this ticket's scatter), the metas in mapped memory, the
   // pool engine's look-back error word as of the decisions it read, the event behind its kernels.
   // route_mu serialises the submits (never held across a wait); the entries are guarded by mu
-  struct RouteEntry {
-    uint64_t ticket = 0;             // the route in flight on this entry (0 = free)
-    bool waiting = false;            // a txv_route_wait is in its event wait
+  struct RouteEntry : RingHead {
     uint32_t G = 0;
     uint32_t n_cap = 0, w_cap = 0;
     uint8_t* d_shard = nullptr;
@@ -338,7 +409,6 @@ struct txv_ctx {
     txv_route_meta *h_meta = nullptr, *m_meta = nullptr;
     uint32_t *h_perr = nullptr, *m_perr = nullptr;   // mapped: the pool engine's error word, written by the scan
     const uint32_t* d_perr_src = nullptr;            // the engine's word in HBM (device-sourced statuses), else null
-    hipEvent_t ev = nullptr;
   } route[kRouteRing];
   std::mutex route_mu;
   uint64_t route_next = 1;           // next route ticket; guarded by mu
@@ -490,9 +560,6 @@ int halloc_mapped(txv_ctx* c, T** p, T** dev, size_t count) {
   if (*p) HIP_TRY(c, hipHostGetDevicePointer((void**)dev, *p, 0));
   return TXV_OK;
 }
-template <typename T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-template <typename T> void hfree(T*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } }
-
 inline uint32_t le32(const uint8_t* p) {
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
@@ -606,10 +673,8 @@ int alloc_tally(txv_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_set_stamp, 0, (size_t)c->cfg.max_txs * 4, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_tab, 0, tab * sizeof(SetEntry), c->stream));
   c->stamp = 0;
-  if (c->d_upd_cnt)   // the Update list's columns are tagged with the stamp, which starts over
-    HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
-  if (c->d_st_tag)    // and so are the store records'
-    HIP_TRY(c, hipMemsetAsync(c->d_st_tag, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
+  HIP_TRY(c, c->upd.clear_tags(c->cfg.max_batch, c->stream));     // tagged with the stamp, which starts over
+  HIP_TRY(c, c->store.clear_tags(c->cfg.max_batch, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_ctr, 0, sizeof(FlowCounters), c->stream));
   c->seq_next = 0;
   c->n_sets_host = 0;
@@ -1007,7 +1072,7 @@ int stage_add(txv_ctx* c, uint32_t slot, const txv_votes* v, bool route = false)
   // a 2-byte code per vote crosses PCIe instead of the 20-byte address and its length
   // (not while the gossip sink is on: its messages carry the address bytes, which must be in HBM,
   // and the code loses an unknown validator's address)
-  const bool host_val = !route && !c->g_msgs && (c->host_val == 1 || (c->host_val < 0 && n >= kHostValMin)) && v->addr &&
+  const bool host_val = !route && !c->gossip.g_msgs && (c->host_val == 1 || (c->host_val < 0 && n >= kHostValMin)) && v->addr &&
                         v->addr_len && c->n_vals < kVcodeEmpty;
   s.host_val = host_val;
   if (!host_val) {
@@ -1113,46 +1178,26 @@ int slot_kernel_ms(txv_ctx* c, Slot& s, float* ms) {
   return TXV_OK;
 }
 
-UpdateSink update_sink(const txv_ctx* c, const Slot& s) {
-  UpdateSink u{};
-  u.cap = c->upd_cap;
-  u.sig = s.u_sig; u.len = s.u_len; u.size = s.u_size; u.set = s.u_set; u.result = s.m_ures;
-  u.cnt = c->d_upd_cnt; u.sid = c->d_upd_sid; u.blk = c->d_upd_blk; u.fired = c->d_upd_fired;
-  return u;
-}
-
-StoreSink store_sink(const txv_ctx* c, const Slot& s) {
-  StoreSink k{};
-  k.cap_bytes = c->st_bytes; k.cap_recs = c->st_recs;
-  k.buf = s.st_buf; k.rec = s.m_strec; k.result = s.m_stres;
-  k.tag = c->d_st_tag; k.rlen = c->d_st_rlen; k.blk = c->d_st_blk; k.fired = c->d_st_fired; k.foff = c->d_st_foff;
-  return k;
-}
-
-GossipSink gossip_sink(const txv_ctx* c, const Slot& s) {
-  GossipSink k{};
-  k.cap_bytes = c->g_bytes; k.cap_msgs = c->g_msgs; k.prefix = c->g_prefix;
-  k.buf = s.g_buf; k.desc = s.g_desc; k.result = s.m_gres;
-  k.ent = c->d_g_ent; k.lay = c->d_g_lay; k.blk = c->d_g_blk;
-  return k;
-}
-
 // the whole AddVote chain of a staged batch: prep (key stream) -> K1a/K1b verify (verify
 // stream), set keying -> new ids -> tally -> results into mapped host memory (flow stream)
 int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   Slot& s = c->slots[slot];
+  // the sinks' state of this slot: the submit ring's slots alone have one (an ingest slot builds nothing)
+  UpdateSinkState::PerSlot* us = slot < kSubmitRing ? &c->upd.slot[slot] : nullptr;
+  StoreSinkState::PerSlot* ss = slot < kSubmitRing ? &c->store.slot[slot] : nullptr;
+  GossipSinkState::PerSlot* gs = slot < kSubmitRing ? &c->gossip.slot[slot] : nullptr;
   if (!s.staged) { c->err = "slot not staged"; return TXV_ESTATE; }
   if (c->poisoned) { c->err = "a TxFlow capacity was exceeded: txv_reset_flow first"; return TXV_ECAPACITY; }
-  if (s.st_reading) { c->err = "a txv_store_records call is still reading this slot's records"; return TXV_ESTATE; }
-  if (s.g_reading) { c->err = "a txv_gossip_msgs call is still reading this slot's messages"; return TXV_ESTATE; }
+  if (ss && ss->reading) { c->err = "a txv_store_records call is still reading this slot's records"; return TXV_ESTATE; }
+  if (gs && gs->reading) { c->err = "a txv_gossip_msgs call is still reading this slot's messages"; return TXV_ESTATE; }
   int r;
   if ((r = ensure_park(c))) return r;
   if (c->stamp == 0xFFFFFFFEu) {   // stamps are about to wrap: forget every candidate first
     const FlowState fs0 = flow_state(c);
     HIP_TRY(c, txv_flow_init_cells(&fs0, (uint64_t)c->cfg.max_txs * std::max<uint32_t>(c->n_vals, 1), 0, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_set_stamp, 0, (size_t)c->cfg.max_txs * 4, c->stream));
-    if (c->d_upd_cnt) HIP_TRY(c, hipMemsetAsync(c->d_upd_cnt, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
-    if (c->d_st_tag) HIP_TRY(c, hipMemsetAsync(c->d_st_tag, 0, (size_t)c->cfg.max_batch * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, c->upd.clear_tags(c->cfg.max_batch, c->stream));
+    HIP_TRY(c, c->store.clear_tags(c->cfg.max_batch, c->stream));
     c->stamp = 0;
   }
   s.stamp = ++c->stamp;            // every run of a batch gets a stamp of its own
@@ -1164,10 +1209,8 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
     for (Slot& o : c->slots)
       if (o.d_ev_tiles) HIP_TRY(c, hipMemsetAsync(o.d_ev_tiles, 0, (size_t)o.ev_tiles_n * sizeof(uint64_t), c->stream));
   s.run_seq = ++c->run_seq;
-  s.u_built = false;               // the slot's earlier list is gone with this run
-  s.u_ticket = 0;
-  s.st_built = false;
-  s.g_built = false;
+  s.sink_ticket = 0;               // the slot's earlier list, records and messages are gone with this run
+  if (slot < kSubmitRing) us->built = ss->built = gs->built = false;
   const FlowState fs = flow_state(c);
   const FlowBatch fb = flow_batch(c, s);
   // Three compute queues, so that batch k+1 verifies while batch k tallies and nothing but
@@ -1218,9 +1261,9 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   // this batch's verify ends.  The chain reads only the raw columns, which the stream's wait for
   // ev[3] above covers (uploads, fills, a CheckTx batch's signatures and nil column) and nothing
   // rewrites before the slot's next staging (which waits for ev[4])
-  if (c->g_msgs && s.g_buf && !s.host_val) {
-    HIP_TRY(c, txv_flow_gossip_msgs(&fb, gossip_sink(c, s), c->stream));
-    s.g_built = true;
+  if (c->gossip.g_msgs && gs && gs->buf && !s.host_val) {
+    HIP_TRY(c, txv_flow_gossip_msgs(&fb, c->gossip.args(slot), c->stream));
+    gs->built = true;
   }
   // set ids in use after this batch: at most those known at the newest fetched run + one per
   // vote of every run not fetched yet (a bound for the touched-set scan).  A slot run again
@@ -1235,19 +1278,19 @@ int run_slot(txv_ctx* c, uint32_t slot, float* ms) {
   if (s.sink) HIP_TRY(c, txv_flow_pack(&fs, s.sink, (s.sink_cap + 31) / 32, s.sink_cap, c->stream));
   // txv_update_sink_enable: the batch's Update list (registries the builder ranks in LDS; a larger
   // one leaves the slot without a list, which txv_update_list reports)
-  if (c->upd_cap && s.u_sig && c->n_vals <= TXV_UPD_MAX_VALS) {
-    if (s.u_cons) {                // a pool still copies the slot's previous list out
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, s.u_cons_ev, 0));
-      s.u_cons = false;
+  if (c->upd.upd_cap && us && us->sig && c->n_vals <= TXV_UPD_MAX_VALS) {
+    if (us->cons) {                // a pool still copies the slot's previous list out
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, us->cons_ev, 0));
+      us->cons = false;
     }
-    HIP_TRY(c, txv_flow_update_list(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), update_sink(c, s), c->stream));
-    s.u_built = true;
+    HIP_TRY(c, txv_flow_update_list(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), c->upd.args(slot), c->stream));
+    us->built = true;
   }
   // txv_store_sink_enable: the batch's SaveTx records (the same registries; txv_store_records reports
   // a larger one)
-  if (c->st_recs && s.st_buf && c->n_vals <= TXV_UPD_MAX_VALS) {
-    HIP_TRY(c, txv_flow_store_records(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), store_sink(c, s), c->stream));
-    s.st_built = true;
+  if (c->store.st_recs && ss && ss->buf && c->n_vals <= TXV_UPD_MAX_VALS) {
+    HIP_TRY(c, txv_flow_store_records(&fs, &fb, txv_flow_n_stamped(&fs, &fb, sets_bound), c->store.args(slot), c->stream));
+    ss->built = true;
   }
   HIP_TRY(c, hipEventRecord(s.ev[4], c->stream));
   s.ran = true;
@@ -1496,18 +1539,29 @@ int run_verify(txv_ctx* c, Slot& s, const KeySet& ks, std::vector<uint8_t>& ok) 
 // batch k+2's host pass and staging run while batch k+1 uploads and batch k computes, so the
 // host pass does not leave the link idle between uploads (two slots: 428.5M votes/s end to end,
 // the host pass between a wait and the next upload)
-int submit_votes(txv_ctx* c, const txv_votes* v, uint64_t* ticket) {
-  const uint64_t t = c->next_ticket;
-  const uint32_t slot = (uint32_t)((t - 1) % kSubmitRing);
+// the ring slot of the next ticket (c->mu held; every submit path holds sub_mu from here to its
+// submit_commit, so the ticket is the same there)
+int submit_ring_slot(txv_ctx* c, uint32_t* slot) {
+  *slot = (uint32_t)((c->next_ticket - 1) % kSubmitRing);
+  if (c->slots[*slot].ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  return TXV_OK;
+}
+
+// the slot's chain is enqueued (run_slot): it is the next ticket's, for the wait and for the sinks
+void submit_commit(txv_ctx* c, uint32_t slot, uint64_t* ticket) {
   Slot& s = c->slots[slot];
-  if (s.ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
-  int r;
-  if ((r = stage_add(c, slot, v))) return r;
-  if ((r = run_slot(c, slot, nullptr))) return r;
+  const uint64_t t = c->next_ticket;
   s.ticket = t;
-  s.u_ticket = t;
+  s.sink_ticket = t;
   c->next_ticket = t + 1;
   *ticket = t;
+}
+
+int submit_votes(txv_ctx* c, const txv_votes* v, uint64_t* ticket) {
+  uint32_t slot;
+  int r;
+  if ((r = submit_ring_slot(c, &slot)) || (r = stage_add(c, slot, v)) || (r = run_slot(c, slot, nullptr))) return r;
+  submit_commit(c, slot, ticket);
   return TXV_OK;
 }
 
@@ -1524,6 +1578,53 @@ int wait_votes(txv_ctx* c, uint64_t ticket, uint8_t* status_out, txv_commit_even
     }
   s.ticket = 0;
   return fetch_slot(c, slot, status_out, ev, ev_cap, n_ev);
+}
+
+// ---- the route and the sign ring's ticket protocol (RingHead) ----
+
+// The wait for `ticket` on its entry e, called and left with g (c->mu) held: the entry is claimed, its
+// event waited for with no lock held, and the entry freed -- also when the wait failed -- before the
+// caller reads what is its own behind the event.  fn and no_ticket: the entry point's words in the errors
+int ring_wait(txv_ctx* c, RingHead& e, std::unique_lock<std::mutex>& g, uint64_t ticket, const char* fn,
+              const char* no_ticket) {
+  if (e.ticket != ticket || e.waiting) { c->err = no_ticket; return TXV_ESTATE; }
+  e.waiting = true;
+  const hipEvent_t done = e.ev;
+  g.unlock();
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipEventSynchronize(done);
+  g.lock();
+  e.ticket = 0;
+  e.waiting = false;
+  if (he != hipSuccess) {
+    c->err = std::string(fn) + ": " + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
+  return TXV_OK;
+}
+
+// the ring's chains still in flight have ended (txv_sync, txv_reset_flow, txv_destroy; c->mu held);
+// their tickets stay waitable
+template <typename E, size_t N>
+int ring_drain(txv_ctx* c, E (&ring)[N]) {
+  for (RingHead& e : ring)
+    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
+  return TXV_OK;
+}
+
+// A synchronous call (submit + wait in one) that leaves the ring idle takes its entry again next
+// time: the next ticket is t + N, on entry (t - 1) % N like t.  A caller that never pipelines then
+// keeps to one entry's slot, staging and scratch (one allocation, warm buffers), as before the
+// rings.  Skipped while a submit is under way (it holds submit_mu and has read `next`).
+template <typename E, size_t N>
+void ring_sync_done(txv_ctx* c, E (&ring)[N], std::mutex& submit_mu, uint64_t& next, uint64_t t) {
+  std::unique_lock<std::mutex> sl(submit_mu, std::try_to_lock);
+  if (!sl.owns_lock()) return;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (next != t + 1) return;
+  for (const RingHead& e : ring)
+    if (e.ticket) return;
+  next = t + N;
 }
 
 // The context's four streams.  Experiment knobs (environment, read once per context):
@@ -1631,16 +1732,14 @@ int txv_init(const txv_config* cfg, txv_ctx** out) {
 void txv_destroy(txv_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (auto& e : c->route)   // routes still in flight write the caller's buffers and the entries' scratch
-    if (e.ticket && e.ev) (void)hipEventSynchronize(e.ev);
-  for (auto& e : c->sign)    // signs still in flight read the entries' staging and write the caller's buffer
-    if (e.ticket && e.ev) (void)hipEventSynchronize(e.ev);
+  (void)ring_drain(c, c->route);   // routes still in flight write the caller's buffers and the entries' scratch
+  (void)ring_drain(c, c->sign);    // signs still in flight read the entries' staging and write the caller's buffer
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
   if (c->vstream) (void)hipStreamSynchronize(c->vstream);
-  if (c->store_stream) (void)hipStreamSynchronize(c->store_stream);
-  if (c->gossip_stream) (void)hipStreamSynchronize(c->gossip_stream);
+  if (c->store.stream) (void)hipStreamSynchronize(c->store.stream);
+  if (c->gossip.stream) (void)hipStreamSynchronize(c->gossip.stream);
   for (auto& s : c->slots) {
     dfree(s.d_sig); dfree(s.d_msg); dfree(s.d_msg_len); dfree(s.d_val); dfree(s.d_set); dfree(s.d_flags);
     dfree(s.d_status); dfree(s.d_ok); dfree(s.d_pre); dfree(s.d_kbuf); dfree(s.d_rpts); dfree(s.d_order); hfree(s.h_order);
@@ -1651,15 +1750,9 @@ void txv_destroy(txv_ctx* c) {
     dfree(s.d_entry); dfree(s.d_blk); dfree(s.d_ev_flag); dfree(s.d_mark); dfree(s.d_stamped); dfree(s.d_ev_tiles); hfree(s.h_ev); hfree(s.h_sum);
     hfree(s.h_fh); hfree(s.h_fs); hfree(s.h_fn); hfree(s.h_fo); hfree(s.h_fl); hfree(s.h_arena);
     dfree(s.d_fh); dfree(s.d_fs); dfree(s.d_fn); dfree(s.d_fo); dfree(s.d_fl); dfree(s.d_arena_th);
-    dfree(s.u_sig); dfree(s.u_len); dfree(s.u_size); dfree(s.u_set); hfree(s.h_ures);
-    if (s.u_cons_ev) (void)hipEventDestroy(s.u_cons_ev);
-    dfree(s.st_buf); hfree(s.h_strec); hfree(s.h_stres);
-    dfree(s.g_buf); dfree(s.g_desc); hfree(s.h_gdesc); hfree(s.h_gres);
     for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
   }
-  dfree(c->d_upd_cnt); dfree(c->d_upd_blk); dfree(c->d_upd_sid); dfree(c->d_upd_fired); dfree(c->d_upd_keys);
-  dfree(c->d_st_tag); dfree(c->d_st_rlen); dfree(c->d_st_blk); dfree(c->d_st_fired); dfree(c->d_st_foff);
-  dfree(c->d_g_ent); dfree(c->d_g_lay); dfree(c->d_g_blk);
+  c->upd.free(); c->store.free(); c->gossip.free();
   dfree(c->d_pubs); dfree(c->d_decode_ok); dfree(c->d_atables); dfree(c->d_vslot); dfree(c->d_addr); dfree(c->d_power);
   dfree(c->d_btable4); dfree(c->d_btable8); dfree(c->d_park); dfree(c->d_wctr); release_base_table(c->device, c->d_btable_wide); c->d_btable = nullptr; dfree(c->d_tmp_pubs); dfree(c->d_tmp_ok); dfree(c->d_tmp_tables); dfree(c->d_tmp_addr);
   dfree(c->d_cells); dfree(c->d_set_cross); dfree(c->d_set_sum);
@@ -1703,8 +1796,6 @@ void txv_destroy(txv_ctx* c) {
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->key_stream) (void)hipStreamDestroy(c->key_stream);
   if (c->vstream) (void)hipStreamDestroy(c->vstream);
-  if (c->store_stream) (void)hipStreamDestroy(c->store_stream);
-  if (c->gossip_stream) (void)hipStreamDestroy(c->gossip_stream);
   delete c;
 }
 
@@ -2407,58 +2498,85 @@ int txv_set_commit_sink(txv_ctx* c, uint32_t slot, void* dst_dev, uint32_t n_set
   return TXV_OK;
 }
 
-int txv_update_sink_enable(txv_ctx* c, uint32_t max_entries) {
-  if (!c) return TXV_EINVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (uint32_t k = 0; k < kSubmitRing; ++k)
-    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
-  // no builder into, and no pool copy out of, the old buffers still pending
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    Slot& s = c->slots[k];
-    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
-    if (s.u_cons) HIP_TRY(c, hipEventSynchronize(s.u_cons_ev));
-    s.u_cons = false;
-    s.u_built = false;
-    s.u_ticket = 0;
-  }
-  c->upd_cap = 0;
-  const size_t m = max_entries, nb = c->cfg.max_batch;
-  int r;
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    Slot& s = c->slots[k];
-    if ((r = dalloc(c, &s.u_sig, 16 * m)) || (r = dalloc(c, &s.u_len, m)) || (r = dalloc(c, &s.u_size, m)) ||
-        (r = dalloc(c, &s.u_set, m)) || (r = halloc_mapped(c, &s.h_ures, &s.m_ures, m ? 4 : 0)))
-      return r;
-    if (m && !s.u_cons_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.u_cons_ev, hipEventDisableTiming));
-  }
-  if ((r = dalloc(c, &c->d_upd_cnt, m ? nb : 0)) || (r = dalloc(c, &c->d_upd_sid, m ? nb : 0)) ||
-      (r = dalloc(c, &c->d_upd_blk, m ? (nb + 1023) / 1024 + 1 : 0)) || (r = dalloc(c, &c->d_upd_fired, m ? 2 * nb : 0)) ||
-      (r = dalloc(c, &c->d_upd_keys, 8 * m)))
-    return r;
-  if (!m) return TXV_OK;
-  HIP_TRY(c, hipMemset(c->d_upd_cnt, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
-  c->upd_cap = max_entries;
-  return TXV_OK;
-}
-
 }  // extern "C"
 
 namespace {
 
-// the slot holding `ticket`'s Update list (c->mu held), or null with c->err set; *n = its entries.
-// TXV_ECAPACITY (*n = the entries it needs) when the batch overflowed the sink.
-int update_list_slot(txv_ctx* c, uint64_t ticket, Slot** out, uint32_t* n) {
+// What every txv_*_sink_enable does before it frees the old buffers (c->mu held): refused while a
+// ring slot has a ticket in flight; then no builder into the old buffers is still pending
+int sink_ring_idle(txv_ctx* c) {
+  for (uint32_t k = 0; k < kSubmitRing; ++k)
+    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
+  for (uint32_t k = 0; k < kSubmitRing; ++k)
+    if (c->slots[k].launched) HIP_TRY(c, hipEventSynchronize(c->slots[k].ev[4]));
+  return TXV_OK;
+}
+
+// The ring slot holding what sink k built for `ticket` (c->mu held), or c->err set.  `on`: the
+// sink's capacity; off, what and not_built: the sink's own words in the messages
+template <typename Sink>
+int sink_slot(txv_ctx* c, const Sink& k, bool on, uint64_t ticket, const char* off, const char* what,
+              const char* not_built, uint32_t* slot) {
+  if (!on) { c->err = off; return TXV_ESTATE; }
+  if (!ticket) return TXV_EINVAL;
+  const uint32_t i = (uint32_t)((ticket - 1) % kSubmitRing);
+  const Slot& s = c->slots[i];
+  if (s.sink_ticket != ticket) { c->err = std::string("no ") + what + " for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
+  if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
+  if (!k.slot[i].built) { c->err = not_built; return TXV_ESTATE; }
+  *slot = i;
+  return TXV_OK;
+}
+
+// A sink's read-out, called and left with g (c->mu) held.  The copies run with no lock held: only what
+// is used, on the read-out's own stream st behind the ticket's completion event `done` (already reached:
+// the ticket was waited for), so nothing in flight on the flow or verify stream is waited for.  `reading`
+// refuses the slot's next submit meanwhile.  enqueue(st) queues the copies; landed() runs behind them
+template <typename Enqueue, typename Landed>
+int sink_read_out(txv_ctx* c, std::unique_lock<std::mutex>& g, hipStream_t st, hipEvent_t done, uint32_t& reading,
+                  const char* fn, Enqueue enqueue, Landed landed) {
+  ++reading;
+  g.unlock();
+  hipError_t he = hipSetDevice(c->device);
+  if (he == hipSuccess) he = hipStreamWaitEvent(st, done, 0);
+  if (he == hipSuccess) he = enqueue(st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he == hipSuccess) landed();
+  g.lock();
+  --reading;
+  if (he != hipSuccess) {
+    c->err = std::string(fn) + ": " + hipGetErrorString(he);
+    return TXV_EDEVICE;
+  }
+  return TXV_OK;
+}
+
+// amino nameToDisfix("tendermint/txvotepool/TxVoteMessage") (go-amino, external): SHA-256 of the
+// registered name, leading zero bytes skipped, 3 disambiguation bytes, zero bytes skipped, 4 prefix bytes
+void txvote_msg_disfix(uint32_t* disamb, uint32_t* prefix) {
+  static const char name[] = "tendermint/txvotepool/TxVoteMessage";
+  uint8_t h[32];
+  txv_sha256_bytes(reinterpret_cast<const uint8_t*>(name), sizeof name - 1, h);
+  int i = 0;
+  while (h[i] == 0) ++i;
+  *disamb = (uint32_t)h[i] | ((uint32_t)h[i + 1] << 8) | ((uint32_t)h[i + 2] << 16);
+  i += 3;
+  while (h[i] == 0) ++i;
+  *prefix = le32(h + i);
+}
+
+// the slot state holding `ticket`'s Update list (c->mu held), or null with c->err set; *n = its
+// entries.  TXV_ECAPACITY (*n = the entries it needs) when the batch overflowed the sink.
+int update_list_slot(txv_ctx* c, uint64_t ticket, UpdateSinkState::PerSlot** out, uint32_t* n) {
   *out = nullptr;
   *n = 0;
-  if (!c->upd_cap) { c->err = "the Update sink is off (txv_update_sink_enable)"; return TXV_ESTATE; }
-  if (!ticket) return TXV_EINVAL;
-  Slot& s = c->slots[(ticket - 1) % kSubmitRing];
-  if (s.u_ticket != ticket) { c->err = "no Update list for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
-  if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
-  if (!s.u_built) { c->err = "no Update list was built: more than 1024 validators"; return TXV_ESTATE; }
+  uint32_t k;
+  if (int r = sink_slot(c, c->upd, c->upd.upd_cap != 0, ticket, "the Update sink is off (txv_update_sink_enable)",
+                        "Update list", "no Update list was built: more than 1024 validators", &k))
+    return r;
+  UpdateSinkState::PerSlot& s = c->upd.slot[k];
   uint32_t res[4];
-  memcpy(res, (const void*)s.h_ures, sizeof res);   // written over PCIe before the slot's ev[4]
+  memcpy(res, (const void*)s.h_res, sizeof res);   // written over PCIe before the slot's ev[4]
   *out = &s;
   if (res[3]) {
     *n = res[2];
@@ -2473,21 +2591,53 @@ int update_list_slot(txv_ctx* c, uint64_t ticket, Slot** out, uint32_t* n) {
 
 extern "C" {
 
+int txv_update_sink_enable(txv_ctx* c, uint32_t max_entries) {
+  if (!c) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  UpdateSinkState& u = c->upd;
+  int r;
+  if ((r = sink_ring_idle(c))) return r;
+  for (uint32_t k = 0; k < kSubmitRing; ++k) {   // ... and no pool copy out of them
+    UpdateSinkState::PerSlot& s = u.slot[k];
+    if (s.cons) HIP_TRY(c, hipEventSynchronize(s.cons_ev));
+    s.cons = false;
+    s.built = false;
+    c->slots[k].sink_ticket = 0;
+  }
+  u.upd_cap = 0;
+  const size_t m = max_entries, nb = c->cfg.max_batch;
+  for (UpdateSinkState::PerSlot& s : u.slot) {
+    if ((r = dalloc(c, &s.sig, 16 * m)) || (r = dalloc(c, &s.len, m)) || (r = dalloc(c, &s.size, m)) ||
+        (r = dalloc(c, &s.set, m)) || (r = halloc_mapped(c, &s.h_res, &s.m_res, m ? 4 : 0)))
+      return r;
+    if (m && !s.cons_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.cons_ev, hipEventDisableTiming));
+  }
+  if ((r = dalloc(c, &u.d_cnt, m ? nb : 0)) || (r = dalloc(c, &u.d_sid, m ? nb : 0)) ||
+      (r = dalloc(c, &u.d_blk, m ? (nb + 1023) / 1024 + 1 : 0)) || (r = dalloc(c, &u.d_fired, m ? 2 * nb : 0)) ||
+      (r = dalloc(c, &u.d_keys, 8 * m)))
+    return r;
+  if (!m) return TXV_OK;
+  HIP_TRY(c, hipMemset(u.d_cnt, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
+  u.upd_cap = max_entries;
+  return TXV_OK;
+}
+
 int txv_update_list(txv_ctx* c, uint64_t ticket, uint8_t* sig_out, uint32_t* size_out, uint32_t* set_out, uint32_t cap,
                     uint32_t* n_out) {
   if (!c) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  Slot* s;
+  UpdateSinkState::PerSlot* s;
   uint32_t n;
   const int r = update_list_slot(c, ticket, &s, &n);
   if (n_out) *n_out = n;
   if (r) return r;
   if (!n || (!sig_out && !size_out && !set_out)) return TXV_OK;
   if (cap < n) { c->err = "txv_update_list: the output arrays are smaller than the list"; return TXV_ECAPACITY; }
-  if (sig_out) HIP_TRY(c, hipMemcpy(sig_out, s->u_sig, (size_t)n * 64, hipMemcpyDeviceToHost));
-  if (size_out) HIP_TRY(c, hipMemcpy(size_out, s->u_size, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (set_out) HIP_TRY(c, hipMemcpy(set_out, s->u_set, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (sig_out) HIP_TRY(c, hipMemcpy(sig_out, s->sig, (size_t)n * 64, hipMemcpyDeviceToHost));
+  if (size_out) HIP_TRY(c, hipMemcpy(size_out, s->size, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (set_out) HIP_TRY(c, hipMemcpy(set_out, s->set, (size_t)n * 4, hipMemcpyDeviceToHost));
   return TXV_OK;
 }
 
@@ -2495,35 +2645,29 @@ int txv_store_sink_enable(txv_ctx* c, uint64_t max_bytes, uint32_t max_records) 
   if (!c || (max_bytes != 0) != (max_records != 0)) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
-    if (c->slots[k].st_reading) { c->err = "a txv_store_records call is still reading the sink"; return TXV_ESTATE; }
-  }
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {   // no builder into the old buffers still pending
-    Slot& s = c->slots[k];
-    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
-    s.st_built = false;
-  }
-  c->st_bytes = 0;
-  c->st_recs = 0;
+  StoreSinkState& k = c->store;
+  for (const StoreSinkState::PerSlot& s : k.slot)
+    if (s.reading) { c->err = "a txv_store_records call is still reading the sink"; return TXV_ESTATE; }
+  int r;
+  if ((r = sink_ring_idle(c))) return r;
+  for (StoreSinkState::PerSlot& s : k.slot) s.built = false;
+  k.st_bytes = 0;
+  k.st_recs = 0;
   const size_t m = max_records, nb = c->cfg.max_batch;
   const size_t bytes = (size_t)((max_bytes + 15) & ~15ull);
-  int r;
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    Slot& s = c->slots[k];
-    if ((r = dalloc(c, &s.st_buf, bytes)) || (r = halloc_mapped(c, &s.h_strec, &s.m_strec, m)) ||
-        (r = halloc_mapped(c, &s.h_stres, &s.m_stres, m ? 8 : 0)))
+  for (StoreSinkState::PerSlot& s : k.slot)
+    if ((r = dalloc(c, &s.buf, bytes)) || (r = halloc_mapped(c, &s.h_rec, &s.m_rec, m)) ||
+        (r = halloc_mapped(c, &s.h_res, &s.m_res, m ? 8 : 0)))
       return r;
-  }
-  if ((r = dalloc(c, &c->d_st_tag, m ? nb : 0)) || (r = dalloc(c, &c->d_st_rlen, m ? nb : 0)) ||
-      (r = dalloc(c, &c->d_st_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0)) || (r = dalloc(c, &c->d_st_fired, m ? nb : 0)) ||
-      (r = dalloc(c, &c->d_st_foff, m ? nb + 1 : 0)))
+  if ((r = dalloc(c, &k.d_tag, m ? nb : 0)) || (r = dalloc(c, &k.d_rlen, m ? nb : 0)) ||
+      (r = dalloc(c, &k.d_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0)) || (r = dalloc(c, &k.d_fired, m ? nb : 0)) ||
+      (r = dalloc(c, &k.d_foff, m ? nb + 1 : 0)))
     return r;
   if (!m) return TXV_OK;
-  if (!c->store_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
-  HIP_TRY(c, hipMemset(c->d_st_tag, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
-  c->st_bytes = max_bytes & ~15ull;   // records start and end at multiples of 16
-  c->st_recs = max_records;
+  if (!k.stream) HIP_TRY(c, hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
+  HIP_TRY(c, hipMemset(k.d_tag, 0, nb * sizeof(uint64_t)));   // stamp 0: no batch's tag
+  k.st_bytes = max_bytes & ~15ull;   // records start and end at multiples of 16
+  k.st_recs = max_records;
   return TXV_OK;
 }
 
@@ -2532,96 +2676,62 @@ int txv_store_records(txv_ctx* c, uint64_t ticket, uint8_t* out, uint64_t cap, u
   if (!c) return TXV_EINVAL;
   if (n_out) *n_out = 0;
   if (bytes_out) *bytes_out = 0;
-  Slot* sp;
-  uint32_t n;
-  uint64_t bytes;
-  hipEvent_t done;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->st_recs) { c->err = "the store sink is off (txv_store_sink_enable)"; return TXV_ESTATE; }
-    if (!ticket) return TXV_EINVAL;
-    Slot& s = c->slots[(ticket - 1) % kSubmitRing];
-    if (s.u_ticket != ticket) { c->err = "no store records for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
-    if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
-    if (!s.st_built) { c->err = "no store records were built: more than 1024 validators"; return TXV_ESTATE; }
-    uint32_t res[8];
-    memcpy(res, (const void*)s.h_stres, sizeof res);   // written over PCIe before the slot's ev[4]
-    const bool over = res[2] != 0;
-    n = over ? res[1] : res[0];
-    bytes = over ? ((uint64_t)res[7] << 32 | res[6]) : ((uint64_t)res[5] << 32 | res[4]);
-    if (n_out) *n_out = n;
-    if (bytes_out) *bytes_out = bytes;
-    if (over) { c->err = "the batch's store records exceed the sink's max_bytes or max_records"; return TXV_ECAPACITY; }
-    if ((out && cap < bytes) || ((off_out || lens_out || set_out) && rec_cap < n)) {
-      c->err = "txv_store_records: the output arrays are smaller than the records";
-      return TXV_ECAPACITY;
-    }
-    for (uint32_t k = 0; k < n; ++k) {               // (mapped host memory: no copy to wait for)
-      const StoreRec& m = s.h_strec[k];
-      if (off_out) off_out[k] = m.off;
-      if (lens_out) memcpy(lens_out + 4 * (size_t)k, m.len, 16);
-      if (set_out) set_out[k] = m.set;
-    }
-    if (!out || !bytes) return TXV_OK;
-    ++s.st_reading;                                    // the slot's next submit is refused meanwhile
-    sp = &s;
-    done = s.ev[4];
+  std::unique_lock<std::mutex> g(c->mu);
+  uint32_t slot;
+  if (int r = sink_slot(c, c->store, c->store.st_recs != 0, ticket, "the store sink is off (txv_store_sink_enable)",
+                        "store records", "no store records were built: more than 1024 validators", &slot))
+    return r;
+  StoreSinkState::PerSlot& s = c->store.slot[slot];
+  uint32_t res[8];
+  memcpy(res, (const void*)s.h_res, sizeof res);   // written over PCIe before the slot's ev[4]
+  const bool over = res[2] != 0;
+  const uint32_t n = over ? res[1] : res[0];
+  const uint64_t bytes = over ? ((uint64_t)res[7] << 32 | res[6]) : ((uint64_t)res[5] << 32 | res[4]);
+  if (n_out) *n_out = n;
+  if (bytes_out) *bytes_out = bytes;
+  if (over) { c->err = "the batch's store records exceed the sink's max_bytes or max_records"; return TXV_ECAPACITY; }
+  if ((out && cap < bytes) || ((off_out || lens_out || set_out) && rec_cap < n)) {
+    c->err = "txv_store_records: the output arrays are smaller than the records";
+    return TXV_ECAPACITY;
   }
-  // the copy with no lock held: only the bytes used, on the read-out's own stream behind the
-  // ticket's completion event (already reached: the ticket was waited for), so nothing in flight on
-  // the flow or verify stream is waited for
-  hipError_t he = hipSetDevice(c->device);
-  if (he == hipSuccess) he = hipStreamWaitEvent(c->store_stream, done, 0);
-  if (he == hipSuccess) he = hipMemcpyAsync(out, sp->st_buf, bytes, hipMemcpyDeviceToHost, c->store_stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(c->store_stream);
-  std::lock_guard<std::mutex> g(c->mu);
-  --sp->st_reading;
-  if (he != hipSuccess) {
-    c->err = std::string("txv_store_records: ") + hipGetErrorString(he);
-    return TXV_EDEVICE;
+  for (uint32_t k = 0; k < n; ++k) {               // (mapped host memory: no copy to wait for)
+    const StoreRec& m = s.h_rec[k];
+    if (off_out) off_out[k] = m.off;
+    if (lens_out) memcpy(lens_out + 4 * (size_t)k, m.len, 16);
+    if (set_out) set_out[k] = m.set;
   }
-  return TXV_OK;
+  if (!out || !bytes) return TXV_OK;
+  return sink_read_out(c, g, c->store.stream, c->slots[slot].ev[4], s.reading, "txv_store_records",
+                       [&](hipStream_t st) { return hipMemcpyAsync(out, s.buf, bytes, hipMemcpyDeviceToHost, st); }, [] {});
 }
 
 int txv_gossip_sink_enable(txv_ctx* c, uint64_t max_bytes, uint32_t max_msgs) {
   if (!c || (max_bytes != 0) != (max_msgs != 0)) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    if (c->slots[k].ticket) { c->err = "a txv_submit_votes batch is in flight"; return TXV_ESTATE; }
-    if (c->slots[k].g_reading) { c->err = "a txv_gossip_msgs call is still reading the sink"; return TXV_ESTATE; }
-  }
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {   // no chain into the old buffers still pending
-    Slot& s = c->slots[k];
-    if (s.launched) HIP_TRY(c, hipEventSynchronize(s.ev[4]));
-    s.g_built = false;
-  }
-  c->g_bytes = 0;
-  c->g_msgs = 0;
+  GossipSinkState& k = c->gossip;
+  for (const GossipSinkState::PerSlot& s : k.slot)
+    if (s.reading) { c->err = "a txv_gossip_msgs call is still reading the sink"; return TXV_ESTATE; }
+  int r;
+  if ((r = sink_ring_idle(c))) return r;
+  for (GossipSinkState::PerSlot& s : k.slot) s.built = false;
+  k.g_bytes = 0;
+  k.g_msgs = 0;
   const size_t m = max_msgs, nb = c->cfg.max_batch;
   const size_t bytes = (size_t)((max_bytes + 15) & ~15ull);
-  int r;
-  for (uint32_t k = 0; k < kSubmitRing; ++k) {
-    Slot& s = c->slots[k];
-    if ((r = dalloc(c, &s.g_buf, bytes)) || (r = dalloc(c, &s.g_desc, m)) || (r = halloc(c, &s.h_gdesc, m)) ||
-        (r = halloc_mapped(c, &s.h_gres, &s.m_gres, m ? 8 : 0)))
+  for (GossipSinkState::PerSlot& s : k.slot)
+    if ((r = dalloc(c, &s.buf, bytes)) || (r = dalloc(c, &s.desc, m)) || (r = halloc(c, &s.h_desc, m)) ||
+        (r = halloc_mapped(c, &s.h_res, &s.m_res, m ? 8 : 0)))
       return r;
-  }
-  if ((r = dalloc(c, &c->d_g_ent, m ? nb : 0)) || (r = dalloc(c, &c->d_g_lay, m ? nb : 0)) || (r = dalloc(c, &c->d_g_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0))) return r;
+  if ((r = dalloc(c, &k.d_ent, m ? nb : 0)) || (r = dalloc(c, &k.d_lay, m ? nb : 0)) ||
+      (r = dalloc(c, &k.d_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0)))
+    return r;
   if (!m) return TXV_OK;
-  if (!c->gossip_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->gossip_stream, hipStreamNonBlocking));
-  // amino nameToDisfix("tendermint/txvotepool/TxVoteMessage"): SHA-256 of the registered name, zero
-  // bytes skipped, 3 disambiguation bytes, zero bytes skipped, 4 prefix bytes (as txv_encode_msgs)
-  static const char name[] = "tendermint/txvotepool/TxVoteMessage";
-  uint8_t h[32];
-  txv_sha256_bytes(reinterpret_cast<const uint8_t*>(name), sizeof name - 1, h);
-  int i = 0;
-  while (h[i] == 0) ++i;
-  i += 3;
-  while (h[i] == 0) ++i;
-  c->g_prefix = le32(h + i);
-  c->g_bytes = max_bytes & ~15ull;   // messages start and end at multiples of 16
-  c->g_msgs = max_msgs;
+  if (!k.stream) HIP_TRY(c, hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
+  uint32_t disamb;
+  txvote_msg_disfix(&disamb, &k.g_prefix);   // (as txv_encode_msgs)
+  k.g_bytes = max_bytes & ~15ull;   // messages start and end at multiples of 16
+  k.g_msgs = max_msgs;
   return TXV_OK;
 }
 
@@ -2630,61 +2740,47 @@ int txv_gossip_msgs(txv_ctx* c, uint64_t ticket, uint8_t* out, uint64_t cap, uin
   if (!c) return TXV_EINVAL;
   if (n_out) *n_out = 0;
   if (bytes_out) *bytes_out = 0;
-  Slot* sp;
-  uint32_t n;
-  uint64_t bytes;
-  hipEvent_t done;
   const bool want_desc = off_out || len_out || idx_out || flag_out;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->g_msgs) { c->err = "the gossip sink is off (txv_gossip_sink_enable)"; return TXV_ESTATE; }
-    if (!ticket) return TXV_EINVAL;
-    Slot& s = c->slots[(ticket - 1) % kSubmitRing];
-    if (s.u_ticket != ticket) { c->err = "no gossip messages for this ticket: unknown, or its slot was reused"; return TXV_ESTATE; }
-    if (s.ticket == ticket) { c->err = "the ticket has not been waited for (txv_wait_votes)"; return TXV_ESTATE; }
-    if (!s.g_built) { c->err = "no gossip messages were built for this batch: it was staged (txv_stage) with the host validator lookup before the sink was enabled"; return TXV_ESTATE; }
-    uint32_t res[8];
-    memcpy(res, (const void*)s.h_gres, sizeof res);   // written over PCIe before the slot's ev[4]
-    n = res[0];
-    bytes = (uint64_t)res[5] << 32 | res[4];
-    if (n_out) *n_out = n;
-    if (bytes_out) *bytes_out = bytes;
-    if (res[1]) { c->err = "the batch's gossip messages exceed the sink's max_bytes or max_msgs"; return TXV_ECAPACITY; }
-    if ((out && cap < bytes) || (want_desc && msg_cap < n)) {
-      c->err = "txv_gossip_msgs: the output arrays are smaller than the messages";
-      return TXV_ECAPACITY;
-    }
-    if ((!out || !bytes) && (!want_desc || !n)) return TXV_OK;
-    // one read-out per slot at a time: the descriptors pass through the slot's pinned buffer
-    if (s.g_reading) { c->err = "another txv_gossip_msgs call is reading this slot"; return TXV_ESTATE; }
-    ++s.g_reading;                                     // the slot's next submit is refused meanwhile
-    sp = &s;
-    done = s.ev[4];
+  std::unique_lock<std::mutex> g(c->mu);
+  uint32_t slot;
+  if (int r = sink_slot(c, c->gossip, c->gossip.g_msgs != 0, ticket, "the gossip sink is off (txv_gossip_sink_enable)",
+                        "gossip messages",
+                        "no gossip messages were built for this batch: it was staged (txv_stage) with the host validator lookup before the sink was enabled",
+                        &slot))
+    return r;
+  GossipSinkState::PerSlot& s = c->gossip.slot[slot];
+  uint32_t res[8];
+  memcpy(res, (const void*)s.h_res, sizeof res);   // written over PCIe before the slot's ev[4]
+  const uint32_t n = res[0];
+  const uint64_t bytes = (uint64_t)res[5] << 32 | res[4];
+  if (n_out) *n_out = n;
+  if (bytes_out) *bytes_out = bytes;
+  if (res[1]) { c->err = "the batch's gossip messages exceed the sink's max_bytes or max_msgs"; return TXV_ECAPACITY; }
+  if ((out && cap < bytes) || (want_desc && msg_cap < n)) {
+    c->err = "txv_gossip_msgs: the output arrays are smaller than the messages";
+    return TXV_ECAPACITY;
   }
-  // the copies with no lock held: only the bytes and descriptors used, on the read-out's own stream
-  // behind the ticket's completion event (already reached: the ticket was waited for), so nothing in
-  // flight on the flow or verify stream is waited for
-  hipError_t he = hipSetDevice(c->device);
-  if (he == hipSuccess) he = hipStreamWaitEvent(c->gossip_stream, done, 0);
-  if (he == hipSuccess && want_desc && n)
-    he = hipMemcpyAsync(sp->h_gdesc, sp->g_desc, (size_t)n * sizeof(GossipDesc), hipMemcpyDeviceToHost, c->gossip_stream);
-  if (he == hipSuccess && out && bytes) he = hipMemcpyAsync(out, sp->g_buf, bytes, hipMemcpyDeviceToHost, c->gossip_stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(c->gossip_stream);
-  if (he == hipSuccess && want_desc)
-    for (uint32_t k = 0; k < n; ++k) {
-      const GossipDesc d = sp->h_gdesc[k];
-      if (off_out) off_out[k] = (uint64_t)d.off_hi << 32 | (d.off_lo & ~15u);
-      if (len_out) len_out[k] = d.len;
-      if (idx_out) idx_out[k] = d.idx;
-      if (flag_out) flag_out[k] = (uint8_t)(d.off_lo & 15u);
-    }
-  std::lock_guard<std::mutex> g(c->mu);
-  --sp->g_reading;
-  if (he != hipSuccess) {
-    c->err = std::string("txv_gossip_msgs: ") + hipGetErrorString(he);
-    return TXV_EDEVICE;
-  }
-  return TXV_OK;
+  if ((!out || !bytes) && (!want_desc || !n)) return TXV_OK;
+  // one read-out per slot at a time: the descriptors pass through the slot's pinned buffer
+  if (s.reading) { c->err = "another txv_gossip_msgs call is reading this slot"; return TXV_ESTATE; }
+  return sink_read_out(
+      c, g, c->gossip.stream, c->slots[slot].ev[4], s.reading, "txv_gossip_msgs",
+      [&](hipStream_t st) {
+        hipError_t he = hipSuccess;
+        if (want_desc && n) he = hipMemcpyAsync(s.h_desc, s.desc, (size_t)n * sizeof(GossipDesc), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess && out && bytes) he = hipMemcpyAsync(out, s.buf, bytes, hipMemcpyDeviceToHost, st);
+        return he;
+      },
+      [&] {
+        if (!want_desc) return;
+        for (uint32_t k = 0; k < n; ++k) {
+          const GossipDesc d = s.h_desc[k];
+          if (off_out) off_out[k] = (uint64_t)d.off_hi << 32 | (d.off_lo & ~15u);
+          if (len_out) len_out[k] = d.len;
+          if (idx_out) idx_out[k] = d.idx;
+          if (flag_out) flag_out[k] = (uint8_t)(d.off_lo & 15u);
+        }
+      });
 }
 
 int txv_slot_kernel_ms(txv_ctx* c, uint32_t slot, float* ms4) {
@@ -2946,23 +3042,9 @@ int route_launch(txv_ctx* c, const txv_votes* v, const uint8_t* st, bool dev_sta
 // txv_route_wait: the entry's event with no lock held, then its metas; frees the entry
 int route_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta) {
   txv_ctx::RouteEntry& e = c->route[(ticket - 1) % kRouteRing];
-  hipEvent_t done;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    if (e.ticket != ticket || e.waiting) { c->err = "txv_route_wait: no such route ticket in flight"; return TXV_ESTATE; }
-    e.waiting = true;
-    done = e.ev;
-  }
-  hipError_t he = hipSetDevice(c->device);
-  if (he == hipSuccess) he = hipEventSynchronize(done);
-  std::lock_guard<std::mutex> g(c->mu);
+  std::unique_lock<std::mutex> g(c->mu);
+  if (int r = ring_wait(c, e, g, ticket, "txv_route_wait", "txv_route_wait: no such route ticket in flight")) return r;
   const uint32_t G = e.G;
-  e.ticket = 0;
-  e.waiting = false;
-  if (he != hipSuccess) {
-    c->err = std::string("txv_route_wait: ") + hipGetErrorString(he);
-    return TXV_EDEVICE;
-  }
   memcpy(meta, e.h_meta, (size_t)G * sizeof(txv_route_meta));
   if (*(volatile uint32_t*)e.h_perr) {   // the pool's statuses the kernels read are not trusted
     c->err = "pool engine: look-back scan timed out (device error; the routed votes were chosen by untrusted statuses)";
@@ -2977,39 +3059,11 @@ int route_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta) {
   return TXV_OK;
 }
 
-// routes still in flight have ended (txv_sync, txv_reset_flow; c->mu held); their tickets stay waitable
-int route_drain(txv_ctx* c) {
-  for (auto& e : c->route)
-    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
-  return TXV_OK;
-}
-
-// the same for the sign ring (txv_sign_txs_submit)
-int sign_drain(txv_ctx* c) {
-  for (auto& e : c->sign)
-    if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
-  return TXV_OK;
-}
-
-// the same for the routed CheckTx ring's key kernels (txv_pool_check_routed_submit)
+// as ring_drain, for the routed CheckTx ring's key kernels (txv_pool_check_routed_submit)
 int routepool_drain(txv_ctx* c) {
   for (auto& e : c->rpool)
     if (e.used && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
   return TXV_OK;
-}
-
-// A synchronous route (submit + wait in one call) that leaves the ring idle takes its entry again
-// next time: the next ticket is t + kRouteRing, on entry (t - 1) % kRouteRing like t.  A caller
-// that never pipelines then keeps to one entry's slot and scratch (one allocation, warm buffers),
-// as before the ring.  Skipped while a submit is under way (it has read route_next).
-void route_sync_done(txv_ctx* c, uint64_t t) {
-  std::unique_lock<std::mutex> rl(c->route_mu, std::try_to_lock);
-  if (!rl.owns_lock()) return;
-  std::lock_guard<std::mutex> g(c->mu);
-  if (c->route_next != t + 1) return;
-  for (const auto& e : c->route)
-    if (e.ticket) return;
-  c->route_next = t + kRouteRing;
 }
 
 int route_submit_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* st, uint32_t G, void* dst, uint64_t stride,
@@ -3155,7 +3209,7 @@ int txv_route_admitted(txv_ctx* c, const txv_votes* v, const uint8_t* pool_statu
   uint64_t t = 0;
   if (int r = route_submit_admitted(c, v, pool_status, n_shards, dst_dev, stride, &t)) return r;
   const int r = route_wait(c, t, meta_out);
-  route_sync_done(c, t);
+  ring_sync_done(c, c->route, c->route_mu, c->route_next, t);
   return r;
 }
 
@@ -3207,17 +3261,12 @@ int txv_submit_routed(txv_ctx* c, const void* buf_dev, const txv_route_meta* met
   std::lock_guard<std::mutex> so(c->sub_mu);   // one submit at a time, as txv_submit_votes: a route wait on
   std::lock_guard<std::mutex> g(c->mu);        // one thread beside a routed submit on another is the normal pattern
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t t = c->next_ticket;
-  const uint32_t slot = (uint32_t)((t - 1) % kSubmitRing);
-  Slot& s = c->slots[slot];
-  if (s.ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  uint32_t slot;
   int r;
-  if ((r = stage_routed(c, slot, static_cast<const uint8_t*>(buf_dev), meta))) return r;
-  if ((r = run_slot(c, slot, nullptr))) return r;
-  s.ticket = t;
-  s.u_ticket = t;
-  c->next_ticket = t + 1;
-  *ticket = t;
+  if ((r = submit_ring_slot(c, &slot)) || (r = stage_routed(c, slot, static_cast<const uint8_t*>(buf_dev), meta)) ||
+      (r = run_slot(c, slot, nullptr)))
+    return r;
+  submit_commit(c, slot, ticket);
   return TXV_OK;
 }
 
@@ -3435,8 +3484,8 @@ int txv_reset_flow(txv_ctx* c) {
   if (!c) return TXV_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  if (int r = route_drain(c)) return r;
-  if (int r = sign_drain(c)) return r;
+  if (int r = ring_drain(c, c->route)) return r;
+  if (int r = ring_drain(c, c->sign)) return r;
   if (int r = routepool_drain(c)) return r;
   if (!c->n_vals) return TXV_OK;
   return reset_tally(c, false);
@@ -3449,8 +3498,8 @@ int txv_sync(txv_ctx* c) {
   {
     std::lock_guard<std::mutex> g(c->mu);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int r = route_drain(c)) return r;
-    if (int r = sign_drain(c)) return r;
+    if (int r = ring_drain(c, c->route)) return r;
+    if (int r = ring_drain(c, c->sign)) return r;
     if (int r = routepool_drain(c)) return r;
   }
   HIP_TRY(c, hipStreamSynchronize(c->vstream));
@@ -3690,38 +3739,11 @@ int sign_submit(txv_ctx* c, const txv_txs* t, uint32_t signer, int64_t height, v
 
 int sign_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta) {
   txv_ctx::SignEntry& e = c->sign[(ticket - 1) % TXV_SIGN_RING];
-  hipEvent_t done;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    if (e.ticket != ticket || e.waiting) { c->err = "txv_sign_txs_wait: no such sign ticket in flight"; return TXV_ESTATE; }
-    e.waiting = true;
-    done = e.ev;
-  }
-  hipError_t he = hipSetDevice(c->device);
-  if (he == hipSuccess) he = hipEventSynchronize(done);
-  std::lock_guard<std::mutex> g(c->mu);
-  e.ticket = 0;
-  e.waiting = false;
-  if (he != hipSuccess) {
-    c->err = std::string("txv_sign_txs_wait: ") + hipGetErrorString(he);
-    return TXV_EDEVICE;
-  }
+  std::unique_lock<std::mutex> g(c->mu);
+  if (int r = ring_wait(c, e, g, ticket, "txv_sign_txs_wait", "txv_sign_txs_wait: no such sign ticket in flight")) return r;
   (void)hipEventElapsedTime(&c->sign_ms, e.ev0, e.ev);
   *meta = e.meta;
   return TXV_OK;
-}
-
-// A synchronous sign (submit + wait in one call) that leaves the ring idle takes its entry again
-// next time, as route_sync_done does for the route ring: a caller that never pipelines keeps to one
-// entry's staging and scratch.  Skipped while a submit is under way (it has read sign_next).
-void sign_sync_done(txv_ctx* c, uint64_t t) {
-  std::unique_lock<std::mutex> sl(c->sign_mu, std::try_to_lock);
-  if (!sl.owns_lock()) return;
-  std::lock_guard<std::mutex> g(c->mu);
-  if (c->sign_next != t + 1) return;
-  for (const auto& e : c->sign)
-    if (e.ticket) return;
-  c->sign_next = t + TXV_SIGN_RING;
 }
 
 bool sign_args_ok(const txv_txs* t, const void* dst) {
@@ -3752,7 +3774,7 @@ int txv_sign_txs(txv_ctx* c, const txv_txs* txs, uint32_t signer, int64_t height
   uint64_t t = 0;
   if (int r = sign_submit(c, txs, signer, height, dst_dev, cap, &t)) return r;
   const int r = sign_wait(c, t, meta_out);
-  sign_sync_done(c, t);
+  ring_sync_done(c, c->sign, c->sign_mu, c->sign_next, t);
   return r;
 }
 
@@ -3819,20 +3841,6 @@ namespace {
 
 // records of txv_k_decode_msgs (TXV_WIRE_REC_WORDS u32 per message, txv_device.h)
 size_t wire_out_bytes(uint32_t cap) { return (size_t)cap * TXV_WIRE_REC_WORDS * 4; }
-
-// amino nameToDisfix("tendermint/txvotepool/TxVoteMessage") (go-amino, external): SHA-256 of the
-// registered name, leading zero bytes skipped, 3 disambiguation bytes, zero bytes skipped, 4 prefix bytes
-void txvote_msg_disfix(uint32_t* disamb, uint32_t* prefix) {
-  static const char name[] = "tendermint/txvotepool/TxVoteMessage";
-  uint8_t h[32];
-  sha256_host(reinterpret_cast<const uint8_t*>(name), sizeof name - 1, h);
-  int i = 0;
-  while (h[i] == 0) ++i;
-  *disamb = (uint32_t)h[i] | ((uint32_t)h[i + 1] << 8) | ((uint32_t)h[i + 2] << 16);
-  i += 3;
-  while (h[i] == 0) ++i;
-  *prefix = le32(h + i);
-}
 
 }  // namespace
 
@@ -5169,13 +5177,13 @@ int pooldev_stage(txv_ctx* c, PoolDev* s, int slot, uint32_t off, const txv_vote
 // pooldev_stage with the entries already in HBM: the n entries of the Update list the context built
 // for `ticket` (txv_update_sink_enable; the ticket waited, so the list is complete) copied device
 // to device into the flight's entries [off, off + n) on the upload stream -- no host copy, no
-// wait.  The context slot's next list build waits for the copies (u_cons_ev, as cons_ev above).
+// wait.  The context slot's next list build waits for the copies (its cons_ev, as cons_ev above).
 int pooldev_stage_dev(txv_ctx* c, PoolDev* s, int slot, uint32_t off, uint64_t ticket, uint32_t n) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (!n) return TXV_OK;
   if ((uint64_t)off + n > s->cap_n) { c->err = "pool device batch above its capacity"; return TXV_ECAPACITY; }
   std::lock_guard<std::mutex> g(c->mu);
-  Slot* src;
+  UpdateSinkState::PerSlot* src;
   uint32_t have;
   if (int r = update_list_slot(c, ticket, &src, &have)) return r;
   if (have != n) { c->err = "the Update list changed under txv_pool_update_fired"; return TXV_ESTATE; }
@@ -5183,12 +5191,12 @@ int pooldev_stage_dev(txv_ctx* c, PoolDev* s, int slot, uint32_t off, uint64_t t
   hipStream_t us = upload_stream(c, engine_stream(c, s));
   f.occ = 0;
   if (f.cons) HIP_TRY(c, hipStreamWaitEvent(us, f.cons_ev, 0));   // a TxFlow chain's reads of the slot first
-  HIP_TRY(c, hipMemcpyAsync(f.d_sig + (size_t)off * 16, src->u_sig, (size_t)n * 64, hipMemcpyDeviceToDevice, us));
-  HIP_TRY(c, hipMemcpyAsync(f.d_len + off, src->u_len, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
-  HIP_TRY(c, hipMemcpyAsync(f.d_sizes + off, src->u_size, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipMemcpyAsync(f.d_sig + (size_t)off * 16, src->sig, (size_t)n * 64, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipMemcpyAsync(f.d_len + off, src->len, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
+  HIP_TRY(c, hipMemcpyAsync(f.d_sizes + off, src->size, (size_t)n * 4, hipMemcpyDeviceToDevice, us));
   HIP_TRY(c, hipEventRecord(f.up_ev, us));
-  HIP_TRY(c, hipEventRecord(src->u_cons_ev, us));
-  src->u_cons = true;
+  HIP_TRY(c, hipEventRecord(src->cons_ev, us));
+  src->cons = true;
   return TXV_OK;
 }
 
@@ -5200,14 +5208,14 @@ int update_list_keys(txv_ctx* c, uint64_t ticket, uint32_t n, std::vector<uint8_
   if (!n) return TXV_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  Slot* src;
+  UpdateSinkState::PerSlot* src;
   uint32_t have;
   if (int r = update_list_slot(c, ticket, &src, &have)) return r;
   if (have != n) { c->err = "the Update list changed under txv_pool_update_fired"; return TXV_ESTATE; }
   hipStream_t ks = c->key_stream;
-  HIP_TRY(c, txv_launch_sig_keys(src->u_sig, src->u_len, n, c->d_upd_keys, ks));
-  HIP_TRY(c, hipMemcpyAsync(keys.data(), c->d_upd_keys, (size_t)n * 32, hipMemcpyDeviceToHost, ks));
-  HIP_TRY(c, hipMemcpyAsync(sizes.data(), src->u_size, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
+  HIP_TRY(c, txv_launch_sig_keys(src->sig, src->len, n, c->upd.d_keys, ks));
+  HIP_TRY(c, hipMemcpyAsync(keys.data(), c->upd.d_keys, (size_t)n * 32, hipMemcpyDeviceToHost, ks));
+  HIP_TRY(c, hipMemcpyAsync(sizes.data(), src->size, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
   HIP_TRY(c, hipStreamSynchronize(ks));
   return TXV_OK;
 }
@@ -5490,8 +5498,8 @@ std::mutex& txv_ctx_submit_mu(txv_ctx* c) { return c->sub_mu; }
 int submit_checked_stage(txv_ctx* c, const txv_votes* v, uint32_t* slot_out) {
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t slot = (uint32_t)((c->next_ticket - 1) % kSubmitRing);
-  if (c->slots[slot].ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  uint32_t slot;
+  if (int r = submit_ring_slot(c, &slot)) return r;
   txv_votes w = *v;
   w.sig = nullptr;                 // from the pool's flight slot (or uploaded late)
   w.is_nil = nullptr;              // written on the device (or uploaded late)
@@ -5541,13 +5549,8 @@ int submit_checked_run(txv_ctx* c, uint32_t slot, const txv_votes* v, const uint
     HIP_TRY(c, hipEventRecord(s.ev[3], c->copy_stream));
   }
   s.has_nil = true;
-  int r;
-  if ((r = run_slot(c, slot, nullptr))) return r;
-  const uint64_t t = c->next_ticket;
-  s.ticket = t;
-  s.u_ticket = t;
-  c->next_ticket = t + 1;
-  *ticket = t;
+  if (int r = run_slot(c, slot, nullptr)) return r;
+  submit_commit(c, slot, ticket);
   return TXV_OK;
 }
 
@@ -5653,8 +5656,8 @@ int routepool_readback(txv_ctx* c, const void* buf, uint64_t bytes, uint8_t* out
 int submit_routed_checked_stage(txv_ctx* c, const void* buf, const txv_route_meta* m, uint32_t* slot_out) {
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t slot = (uint32_t)((c->next_ticket - 1) % kSubmitRing);
-  if (c->slots[slot].ticket) { c->err = "four batches already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+  uint32_t slot;
+  if (int r = submit_ring_slot(c, &slot)) return r;
   if (!c->rp_ks_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->rp_ks_ev, hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(c->rp_ks_ev, c->key_stream));
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->rp_ks_ev, 0));
@@ -5698,13 +5701,8 @@ int submit_routed_checked_run(txv_ctx* c, uint32_t slot, uint32_t n, const uint8
     HIP_TRY(c, hipEventRecord(s.ev[3], cs));
   }
   s.has_nil = true;
-  int r;
-  if ((r = run_slot(c, slot, nullptr))) return r;
-  const uint64_t t = c->next_ticket;
-  s.ticket = t;
-  s.u_ticket = t;
-  c->next_ticket = t + 1;
-  *ticket = t;
+  if (int r = run_slot(c, slot, nullptr)) return r;
+  submit_commit(c, slot, ticket);
   return TXV_OK;
 }
 
@@ -5712,7 +5710,7 @@ std::mutex& txv_ctx_route_mu(txv_ctx* c) { return c->route_mu; }
 bool route_checked_args_ok(const txv_votes* v, uint32_t G, const void* dst, uint64_t stride) {
   return route_args_ok(v, G, dst, stride, true);
 }
-void route_checked_sync_done(txv_ctx* c, uint64_t ticket) { route_sync_done(c, ticket); }
+void route_checked_sync_done(txv_ctx* c, uint64_t t) { ring_sync_done(c, c->route, c->route_mu, c->route_next, t); }
 int route_checked_stage(txv_ctx* c, const txv_votes* v, uint64_t stride) { return route_stage(c, v, true, stride); }
 int route_checked_launch(txv_ctx* c, const txv_votes* v, const uint8_t* host_st, uint32_t G, void* dst, uint64_t stride,
                          uint64_t* ticket) {

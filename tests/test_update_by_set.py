@@ -374,3 +374,27 @@ def test_large_batch_compacted_stamps():
         assert np.array_equal(size, np.where(nanos < 128, s1, np.where(nanos < 16384, s2, s3)).astype(np.uint32))
     finally:
         c.close()
+
+
+# ------------------------------------------------------------------ 9. a routed batch
+def test_routed_batch_list(ctx, cadence):
+    """the list behind plain txv_submit_routed: the batch routed as one shard into a buffer in this
+    device's HBM and submitted from there"""
+    import torch
+    import txflow_amd as T
+    pubs, powers, votes = cadence
+    _start(ctx, pubs, powers, 512)
+    ref = Grouped(pubs, powers)
+    part = votes[:64]
+    exp, est, efired, info = ref.batch(part)
+    assert info["sets"] >= 2 and info["unfired"] >= 1
+    b = _batch(part)
+    stride = T.route_stride(b)
+    dev = torch.zeros(stride, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    metas = ctx.route_admitted(b, None, 1, dev.data_ptr(), stride)
+    assert int(metas[0]["n"]) == len(part)
+    tk = ctx.submit_routed(dev.data_ptr(), metas[0])
+    st, _ = ctx.wait_votes(tk)
+    assert np.array_equal(st, est.astype(np.uint8) | (efired.astype(np.uint8) << 7))
+    _assert_list(ctx.update_list(tk), ref.columns(exp), "routed batch")
