@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "ed25519_dev.h"
+#include "fe_batch_inv.h"
 #include "fe_inv_var.h"
 #include "signbytes_dev.h"
 #include "txv_device.h"
@@ -635,11 +636,43 @@ __global__ void __launch_bounds__(BLOCK, V == 8 ? 2 : TXV_V4_WAVES * BLOCK / 512
 // still held its slots) or that shares its issue slots with one finishes last.  Here every wave
 // takes its work in chunks of 64 work entries (one vote slot per lane) from the counter of its
 // XCD's eighth of the work list, and from the other eighths once its own is drained: up to V
-// chunks share one inversion, and a wave keeps taking chunks (further inversions) while any are
+// chunks form a group that shares one inversion, and a wave keeps taking chunks while any are
 // left.  Each slot parks its lane's vote index beside the point (park word 32).
+//
+// One inversion per BLOCK: under SIMD an inversion costs a wave the same whether its lanes hold 64
+// values or one, and a 1M-vote batch gives every wave exactly one group, so the waves' inversions
+// are shared across the block.  A wave claims its next chunk BEFORE it inverts a full group: only
+// if it gets one (more than V chunks per wave: batches above ~2.1M votes) does it invert that
+// group itself.  Its last group (possibly empty: P = 1) goes to the hand-off after the loop, which
+// every wave of the block reaches exactly once: the waves leave their running products P_w in
+// their entry buffers (idle once the walks are over), wave 0 turns them into 1/P_w with one
+// inversion (fe_batch_inv.h) and each wave walks its group back from its own.
 #ifndef TXV_K1B_DYNAMIC
 #define TXV_K1B_DYNAMIC 1
 #endif
+
+// K1b's hand-off: element i of the chain is wave i's running product, one fe per lane in the first
+// 2 KiB of that wave's entry buffer (word j of lane l at j * 64 + l: conflict-free); the prefix
+// products use the 2 KiB behind it.  b: the block's buffers as words, at this lane.
+template <int WAVE_WORDS>
+struct k1b_handoff_lds {
+  uint32_t* b;
+  __device__ __forceinline__ fe ld(int at) const {
+    fe r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.v[j] = b[at + j * 64];
+    return r;
+  }
+  __device__ __forceinline__ void st(int at, const fe& v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[at + j * 64] = v.v[j];
+  }
+  __device__ __forceinline__ fe x(int i) const { return ld(i * WAVE_WORDS); }
+  __device__ __forceinline__ void set_x(int i, const fe& v) { st(i * WAVE_WORDS, v); }
+  __device__ __forceinline__ fe pre(int i) const { return ld(i * WAVE_WORDS + 512); }
+  __device__ __forceinline__ void set_pre(int i, const fe& v) { st(i * WAVE_WORDS + 512, v); }
+};
+
 template <int BLOCK, int WB, int WA, int V>
 __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
   const uint32_t lane = threadIdx.x & 63;
@@ -649,8 +682,10 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
   const uint32_t gwave = (blockIdx.x * BLOCK + threadIdx.x) >> 6;
   uint32_t* park = a.park + (size_t)gwave * V * TXV_PARK_WORDS * 64 + lane;
   constexpr int PD = 2;
-  __shared__ uint4 pf[BLOCK / 64][PD * 8 * 64];
-  uint4* wbuf = pf[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+  constexpr int kWaves = BLOCK / 64, kWaveWords = PD * 8 * 64 * 4;
+  __shared__ uint4 pf[kWaves][PD * 8 * 64];
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint4* wbuf = pf[wave];
   uint32_t src = 0;                      // ranges tried: (myx + src) % xg
   // the next chunk for this wave (wave-uniform), or 0xFFFFFFFFu when every range is drained
   auto next_chunk = [&]() -> uint32_t {
@@ -665,39 +700,8 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
     }
     return 0xFFFFFFFFu;
   };
-  for (;;) {
-    ge_ext R;
-    fe P;
-    uint32_t h = 0;
-#pragma unroll 1
-    for (; h < (uint32_t)V; ++h) {
-      const uint32_t c = next_chunk();
-      if (c == 0xFFFFFFFFu) break;
-      const uint32_t idx = 64u * c + lane;
-      const uint32_t i = idx < a.n_work ? (a.order ? a.order[idx] : idx) : 0u;
-      const bool on = idx < a.n_work && a.ok_out[i] == 2;
-      uint32_t s[8], k[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s[j] = on ? a.sig[(size_t)(8 + j) * a.n_pad + i] : 0u;
-        k[j] = on ? a.kbuf[(size_t)j * a.n_pad + i] : 0u;
-      }
-      // idle lanes walk the digit-0 (identity) entries of validator 0: the cooperative gathers
-      // need every lane of the wave
-      R = k1b_walk<WB, WA, PD>(a.btable, a.atables, on ? tab_slot(a, a.val[i]) : 0u, s, k, wbuf);
-      P = h ? fe_mul(P, R.Z) : R.Z;
-      uint32_t* slot = park + h * TXV_PARK_WORDS * 64;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        slot[j * 64] = R.X.v[j];
-        slot[(8 + j) * 64] = R.Y.v[j];
-        slot[(16 + j) * 64] = P.v[j];
-        slot[(24 + j) * 64] = R.Z.v[j];
-      }
-      slot[32 * 64] = on ? i + 1u : 0u;
-    }
-    if (h == 0) break;
-    fe inv = verify_invert(P);
+  // slots h-1 .. 0 of the park buffer from inv = 1 / (Z_0 ... Z_{h-1}): encode and compare
+  auto walk_back = [&](fe inv, uint32_t h) {
 #pragma unroll 1
     for (int hh = (int)h - 1; hh >= 0; --hh) {
       const uint32_t* slot = park + hh * TXV_PARK_WORDS * 64;
@@ -729,8 +733,56 @@ __device__ __forceinline__ void k1b_dyn_body(const VerifyArgs& a) {
         a.ok_out[i] = diff == 0;
       }
     }
-    if (h < (uint32_t)V) break;
+  };
+  // No wave leaves this loop other than through its condition: every wave of the block, with or
+  // without work, arrives at the hand-off below.
+  fe P = fe_one();                       // the current group's running product over its h slots
+  uint32_t h = 0;
+#pragma unroll 1
+  for (uint32_t c = next_chunk(); c != 0xFFFFFFFFu; c = next_chunk()) {
+    if (h == (uint32_t)V) {              // a full group and more work behind it: inverted here
+      walk_back(verify_invert(P), h);
+      h = 0;
+    }
+    const uint32_t idx = 64u * c + lane;
+    const uint32_t i = idx < a.n_work ? (a.order ? a.order[idx] : idx) : 0u;
+    const bool on = idx < a.n_work && a.ok_out[i] == 2;
+    uint32_t s[8], k[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s[j] = on ? a.sig[(size_t)(8 + j) * a.n_pad + i] : 0u;
+      k[j] = on ? a.kbuf[(size_t)j * a.n_pad + i] : 0u;
+    }
+    // idle lanes walk the digit-0 (identity) entries of validator 0: the cooperative gathers
+    // need every lane of the wave
+    const ge_ext R = k1b_walk<WB, WA, PD>(a.btable, a.atables, on ? tab_slot(a, a.val[i]) : 0u, s, k, wbuf);
+    P = h ? fe_mul(P, R.Z) : R.Z;
+    uint32_t* slot = park + h * TXV_PARK_WORDS * 64;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      slot[j * 64] = R.X.v[j];
+      slot[(8 + j) * 64] = R.Y.v[j];
+      slot[(16 + j) * 64] = P.v[j];
+      slot[(24 + j) * 64] = R.Z.v[j];
+    }
+    slot[32 * 64] = on ? i + 1u : 0u;
+    ++h;
   }
+  // Block hand-off.  P_w (1 for an empty group) and the group's size go to the wave's own buffer;
+  // every walk of the block has read its entries out before the barrier completes.
+  k1b_handoff_lds<kWaveWords> lds{reinterpret_cast<uint32_t*>(&pf[0][0]) + lane};
+  lds.set_x((int)wave, P);
+  lds.b[wave * kWaveWords + 1024] = h;   // per lane, the same value: word 1024 + lane
+  __syncthreads();
+  uint32_t any = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) any |= lds.b[w * kWaveWords + 1024];
+  // the same LDS words in every wave: a block-uniform decision, so the barrier inside is reached
+  // by all waves or by none
+  if (__builtin_amdgcn_readfirstlane(any) == 0) return;   // no group with work in this block
+  if (wave == 0) fe_invert_each(lds, kWaves, [](const fe& z) { return verify_invert(z); });
+  __syncthreads();
+  if (h) walk_back(lds.x((int)wave), h);
 }
 
 template <int BLOCK, int WB, int WA, int V>
