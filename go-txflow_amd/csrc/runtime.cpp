@@ -21,6 +21,7 @@
 #include "signbytes_dev.h"
 #include "route.h"
 #include "routepool_dev.h"
+#include "load_dev.h"
 
 #include <hip/hip_runtime.h>
 #include <emmintrin.h>
@@ -393,6 +394,29 @@ struct txv_ctx {
   uint64_t sign_next = 1;              // next sign ticket; guarded by mu
   uint64_t sk_gen = 0;                 // txv_keygen calls so far (a sign submit notices new slots)
   float sign_ms = 0.f;                 // device time of the last waited chain (txv_sign_txs_ms)
+  // the load ring (txv_load_commits_submit / txv_load_commits_wait; kernels_load.hip): ticket t on
+  // entry (t - 1) % TXV_LOAD_RING, each with pinned staging and device copies of the records, their
+  // offsets and lengths, the chain's per-record scratch, the per-record outputs and the meta in
+  // mapped host memory, the event behind its uploads (copy stream) and the events around its kernels
+  // (key stream).  load_mu serialises the submits; the entries are guarded by mu
+  struct LoadEntry : RingHead {
+    uint32_t n_cap = 0, n_rec = 0;
+    uint64_t b_cap = 0;
+    uint8_t *h_recs = nullptr, *d_recs = nullptr;
+    uint64_t *h_off = nullptr, *d_off = nullptr;
+    uint32_t *h_len = nullptr, *d_len = nullptr;
+    uint8_t* d_status = nullptr;
+    uint32_t *d_cnt = nullptr, *d_thb = nullptr, *d_maxhl = nullptr, *d_first = nullptr, *d_afirst = nullptr;
+    uint64_t* d_tot = nullptr;
+    uint8_t *h_status = nullptr, *m_status = nullptr;
+    uint32_t *h_first = nullptr, *m_first = nullptr, *h_thlen = nullptr, *m_thlen = nullptr;
+    uint64_t *h_thoff = nullptr, *m_thoff = nullptr;
+    txv_route_meta *h_meta = nullptr, *m_meta = nullptr;
+    hipEvent_t up_ev = nullptr, ev0 = nullptr;
+  } load[TXV_LOAD_RING];
+  std::mutex load_mu;
+  uint64_t load_next = 1;              // next load ticket; guarded by mu
+  float load_ms = 0.f;                 // device time of the last waited load (txv_load_commits_ms)
   Slot slots[kSlots];
   // the route ring (txv_route_submit_* / txv_route_wait; kernels_route.hip): ticket t on entry
   // (t - 1) % kRouteRing with slot kRouteSlot + entry for its columns and its own scratch -- per-vote
@@ -1734,6 +1758,7 @@ void txv_destroy(txv_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)ring_drain(c, c->route);   // routes still in flight write the caller's buffers and the entries' scratch
   (void)ring_drain(c, c->sign);    // signs still in flight read the entries' staging and write the caller's buffer
+  (void)ring_drain(c, c->load);    // ... and so do loads
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->key_stream) (void)hipStreamSynchronize(c->key_stream);
@@ -1770,6 +1795,12 @@ void txv_destroy(txv_ctx* c) {
     hfree(e.h_tx); dfree(e.d_tx); hfree(e.h_off); dfree(e.d_off); hfree(e.h_len); dfree(e.d_len);
     hfree(e.h_sec); dfree(e.d_sec); hfree(e.h_nanos); dfree(e.d_nanos);
     dfree(e.d_msg); dfree(e.d_msg_len); dfree(e.d_r); dfree(e.d_rpts); dfree(e.d_renc);
+    for (hipEvent_t ev : {e.up_ev, e.ev0, e.ev}) if (ev) (void)hipEventDestroy(ev);
+  }
+  for (auto& e : c->load) {
+    hfree(e.h_recs); dfree(e.d_recs); hfree(e.h_off); dfree(e.d_off); hfree(e.h_len); dfree(e.d_len);
+    dfree(e.d_status); dfree(e.d_cnt); dfree(e.d_thb); dfree(e.d_maxhl); dfree(e.d_first); dfree(e.d_afirst); dfree(e.d_tot);
+    hfree(e.h_status); hfree(e.h_first); hfree(e.h_thlen); hfree(e.h_thoff); hfree(e.h_meta);
     for (hipEvent_t ev : {e.up_ev, e.ev0, e.ev}) if (ev) (void)hipEventDestroy(ev);
   }
   for (auto& e : c->rpool) {
@@ -3486,6 +3517,7 @@ int txv_reset_flow(txv_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (int r = ring_drain(c, c->route)) return r;
   if (int r = ring_drain(c, c->sign)) return r;
+  if (int r = ring_drain(c, c->load)) return r;
   if (int r = routepool_drain(c)) return r;
   if (!c->n_vals) return TXV_OK;
   return reset_tally(c, false);
@@ -3500,6 +3532,7 @@ int txv_sync(txv_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = ring_drain(c, c->route)) return r;
     if (int r = ring_drain(c, c->sign)) return r;
+    if (int r = ring_drain(c, c->load)) return r;
     if (int r = routepool_drain(c)) return r;
   }
   HIP_TRY(c, hipStreamSynchronize(c->vstream));
@@ -3581,6 +3614,173 @@ int txv_fe_selftest(txv_ctx* c, const uint32_t* a, const uint32_t* b, uint32_t* 
   HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   dfree(da); dfree(db); dfree(dout);
+  return TXV_OK;
+}
+
+}  // extern "C"
+
+// ---- TxStore.LoadTxCommit for a batch of stored Commit records (tx/store.go:67-80, txflow/service.go:115-120;
+// kernels_load.hip) ----
+namespace {
+
+// the entry's events, staging and per-record scratch for n_rec records of `bytes` bytes
+int ensure_load_entry(txv_ctx* c, txv_ctx::LoadEntry& e, uint32_t n_rec, uint64_t bytes) {
+  int r;
+  if (!e.ev) {
+    HIP_TRY(c, hipEventCreateWithFlags(&e.up_ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreate(&e.ev0));
+    HIP_TRY(c, hipEventCreate(&e.ev));
+  }
+  if (!e.h_meta && ((r = dalloc(c, &e.d_tot, 4)) || (r = halloc_mapped(c, &e.h_meta, &e.m_meta, 1)))) return r;
+  const size_t need = (size_t)n_rec + 1;   // first_vote has n_rec + 1 entries
+  if (e.n_cap < need) {
+    const size_t cap = std::max<size_t>({need, (size_t)e.n_cap * 2, 64});
+    e.n_cap = 0;
+    if ((r = halloc(c, &e.h_off, cap)) || (r = dalloc(c, &e.d_off, cap)) || (r = halloc(c, &e.h_len, cap)) ||
+        (r = dalloc(c, &e.d_len, cap)) || (r = dalloc(c, &e.d_status, cap)) || (r = dalloc(c, &e.d_cnt, cap)) ||
+        (r = dalloc(c, &e.d_thb, cap)) || (r = dalloc(c, &e.d_maxhl, cap)) || (r = dalloc(c, &e.d_first, cap)) ||
+        (r = dalloc(c, &e.d_afirst, cap)) || (r = halloc_mapped(c, &e.h_status, &e.m_status, cap)) ||
+        (r = halloc_mapped(c, &e.h_first, &e.m_first, cap)) || (r = halloc_mapped(c, &e.h_thoff, &e.m_thoff, cap)) ||
+        (r = halloc_mapped(c, &e.h_thlen, &e.m_thlen, cap)))
+      return r;
+    e.n_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
+  }
+  if (e.b_cap < bytes + 128) {   // 128 bytes behind the records: the row copies read whole aligned words
+    const uint64_t cap = (std::max<uint64_t>(bytes + 128, e.b_cap * 2) + 15) & ~15ull;
+    e.b_cap = 0;
+    if ((r = halloc(c, &e.h_recs, cap)) || (r = dalloc(c, &e.d_recs, cap))) return r;
+    e.b_cap = cap;
+  }
+  return TXV_OK;
+}
+
+int load_submit(txv_ctx* c, const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off, const uint32_t* len,
+                uint32_t n, void* dst, uint64_t cap, uint64_t* ticket) {
+  // load_mu: one submit at a time, so the next ticket's entry is this call's from the checks to the
+  // launch; the context's lock is not held while the records are copied into the entry's staging
+  std::lock_guard<std::mutex> lg(c->load_mu);
+  if (recs_bytes >= (1ull << 32)) { c->err = "txv_load_commits: recs_bytes must be below 2^32"; return TXV_EINVAL; }
+  for (uint32_t k = 0; k < n; ++k)
+    if (off[k] > recs_bytes || len[k] > recs_bytes - off[k]) {
+      c->err = "txv_load_commits: record " + std::to_string(k) + " lies outside recs";
+      return TXV_EINVAL;
+    }
+  uint64_t tk = 0;
+  txv_ctx::LoadEntry* ep = nullptr;
+  bool reg = false;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->device));
+    tk = c->load_next;
+    ep = &c->load[(tk - 1) % TXV_LOAD_RING];
+    if (ep->ticket) { c->err = "two loads already in flight: wait for the oldest one first"; return TXV_ESTATE; }
+    if (int r = ensure_load_entry(c, *ep, n, recs_bytes)) return r;
+    reg = recs_bytes && is_registered(c, recs, recs_bytes);
+  }
+  txv_ctx::LoadEntry& e = *ep;   // the free entry's staging is this call's alone (load_mu)
+  if (recs_bytes && !reg) {
+    c->pool->parallel_for((uint32_t)((recs_bytes + 0xFFFFF) >> 20), [&](uint32_t lo, uint32_t hi) {
+      const uint64_t b0 = (uint64_t)lo << 20, b1 = std::min<uint64_t>((uint64_t)hi << 20, recs_bytes);
+      memcpy(e.h_recs + b0, recs + b0, b1 - b0);
+    }, 4);
+  }
+  if (n) {
+    memcpy(e.h_off, off, (size_t)n * 8);
+    memcpy(e.h_len, len, (size_t)n * 4);
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t up = c->copy_stream, ks = c->key_stream;
+  if (recs_bytes) HIP_TRY(c, hipMemcpyAsync(e.d_recs, reg ? recs : e.h_recs, recs_bytes, hipMemcpyHostToDevice, up));
+  HIP_TRY(c, hipMemsetAsync(e.d_recs + recs_bytes, 0, 128, up));
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(e.d_off, e.h_off, (size_t)n * 8, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(e.d_len, e.h_len, (size_t)n * 4, hipMemcpyHostToDevice, up));
+  }
+  HIP_TRY(c, hipEventRecord(e.up_ev, up));
+  HIP_TRY(c, hipStreamWaitEvent(ks, e.up_ev, 0));
+  LoadArgs a{};
+  a.recs = e.d_recs; a.recs_alloc = (recs_bytes + 128) & ~15ull;
+  a.off = e.d_off; a.len = e.d_len; a.n_rec = n;
+  a.dst = static_cast<uint8_t*>(dst); a.cap = cap;
+  a.status = e.d_status; a.cnt = e.d_cnt; a.thb = e.d_thb; a.maxhl = e.d_maxhl; a.first = e.d_first; a.afirst = e.d_afirst;
+  a.tot = e.d_tot;
+  a.m_status = e.m_status; a.m_first = e.m_first; a.m_thoff = e.m_thoff; a.m_thlen = e.m_thlen; a.m_meta = e.m_meta;
+  // the chain reads and writes no TxFlow state: on the key stream, behind the uploads
+  HIP_TRY(c, hipEventRecord(e.ev0, ks));
+  HIP_TRY(c, txv_launch_load_commits(&a, ks));
+  HIP_TRY(c, hipEventRecord(e.ev, ks));
+  e.n_rec = n;
+  e.ticket = tk;
+  e.waiting = false;
+  c->load_next = tk + 1;
+  *ticket = tk;
+  return TXV_OK;
+}
+
+int load_wait(txv_ctx* c, uint64_t ticket, txv_route_meta* meta, uint8_t* st, uint32_t* first, uint64_t* thoff,
+              uint32_t* thlen) {
+  txv_ctx::LoadEntry& e = c->load[(ticket - 1) % TXV_LOAD_RING];
+  std::unique_lock<std::mutex> g(c->mu);
+  if (int r = ring_wait(c, e, g, ticket, "txv_load_commits_wait", "txv_load_commits_wait: no such load ticket in flight"))
+    return r;
+  (void)hipEventElapsedTime(&c->load_ms, e.ev0, e.ev);
+  const size_t n = e.n_rec;   // mu is held: the next submit cannot have the entry yet
+  if (st && n) memcpy(st, e.h_status, n);
+  if (first) memcpy(first, e.h_first, (n + 1) * 4);
+  if (thoff && n) memcpy(thoff, e.h_thoff, n * 8);
+  if (thlen && n) memcpy(thlen, e.h_thlen, n * 4);
+  const txv_route_meta m = *e.h_meta;
+  if (meta) *meta = m;
+  if (m.reserved) {
+    c->err = "txv_load_commits: the buffer needs " + std::to_string(m.bytes) + " bytes (" + std::to_string(m.n) +
+             " votes, " + std::to_string(m.arena_bytes) + " TxHash bytes), above cap: nothing was written";
+    return TXV_ECAPACITY;
+  }
+  return TXV_OK;
+}
+
+bool load_args_ok(const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off, const uint32_t* len, uint32_t n,
+                  const void* dst, uint64_t cap) {
+  if (!dst || (uintptr_t)dst % 16 || cap % 16) return false;
+  return (recs || !recs_bytes) && (!n || (off && len));
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t txv_load_commits_bytes(uint32_t max_votes, uint64_t commit_bytes) {
+  return txv_route_bytes(max_votes, commit_bytes, TXV_ROUTE_TXKEY | TXV_ROUTE_NIL);
+}
+
+int txv_load_commits_submit(txv_ctx* c, const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off, const uint32_t* len,
+                            uint32_t n_records, void* dst_dev, uint64_t cap, uint64_t* load_ticket) {
+  if (!c || !load_ticket || !load_args_ok(recs, recs_bytes, off, len, n_records, dst_dev, cap)) return TXV_EINVAL;
+  return load_submit(c, recs, recs_bytes, off, len, n_records, dst_dev, cap, load_ticket);
+}
+
+int txv_load_commits_wait(txv_ctx* c, uint64_t load_ticket, txv_route_meta* meta_out, uint8_t* rec_status,
+                          uint32_t* first_vote, uint64_t* rec_txhash_off, uint32_t* rec_txhash_len) {
+  if (!c || !load_ticket) return TXV_EINVAL;
+  return load_wait(c, load_ticket, meta_out, rec_status, first_vote, rec_txhash_off, rec_txhash_len);
+}
+
+int txv_load_commits(txv_ctx* c, const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off, const uint32_t* len,
+                     uint32_t n_records, void* dst_dev, uint64_t cap, txv_route_meta* meta_out, uint8_t* rec_status,
+                     uint32_t* first_vote, uint64_t* rec_txhash_off, uint32_t* rec_txhash_len) {
+  if (!c || !load_args_ok(recs, recs_bytes, off, len, n_records, dst_dev, cap)) return TXV_EINVAL;
+  uint64_t t = 0;
+  if (int r = load_submit(c, recs, recs_bytes, off, len, n_records, dst_dev, cap, &t)) return r;
+  const int r = load_wait(c, t, meta_out, rec_status, first_vote, rec_txhash_off, rec_txhash_len);
+  ring_sync_done(c, c->load, c->load_mu, c->load_next, t);
+  return r;
+}
+
+int txv_load_commits_ms(txv_ctx* c, float* ms) {
+  if (!c || !ms) return TXV_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  *ms = c->load_ms;
   return TXV_OK;
 }
 

@@ -93,6 +93,26 @@ class GossipMsgsError(TxvInfraError):
         self.nbytes = nbytes
 
 
+COMMIT_OK, COMMIT_CORRUPT, COMMIT_EMPTY = range(3)   # TXV_COMMIT_*
+
+
+class LoadCommitsError(TxvInfraError):
+    """Context.load_commits / load_commits_wait: the route buffer the records decode to does not fit
+    cap (rc = E_CAPACITY: nothing was written; n = the votes, arena_bytes = the TxHash bytes and
+    nbytes = the buffer size it needs; meta, rec_status and first_vote as the wait returned them),
+    or the call failed otherwise (rc)"""
+
+    def __init__(self, what, rc, msg, meta=None, rec_status=None, first_vote=None):
+        super().__init__(f"{what} failed ({rc}): {msg}")
+        self.rc = rc
+        self.meta = meta
+        self.n = int(meta["n"]) if meta is not None else 0
+        self.arena_bytes = int(meta["arena_bytes"]) if meta is not None else 0
+        self.nbytes = int(meta["bytes"]) if meta is not None else 0
+        self.rec_status = rec_status
+        self.first_vote = first_vote
+
+
 class RouteGuardError(TxvInfraError):
     """TxVotePool.check_wait / check_routed of a route buffer whose header was not the one its meta
     described (TXV_EINVAL): the kernel touched nothing beyond the header and the pool is unchanged.
@@ -156,6 +176,7 @@ ROUTE_META_DTYPE = np.dtype([("n", "<u4"), ("max_txhash_len", "<u4"), ("flags", 
 ROUTE_TXKEY, ROUTE_NIL = 0x1, 0x2
 ROUTE_RING = 4   # TXV_ROUTE_RING: route tickets in flight per context
 SIGN_RING = 2    # TXV_SIGN_RING: sign tickets in flight per context
+LOAD_RING = 2    # TXV_LOAD_RING: load tickets in flight per context
 
 
 _lib = None
@@ -303,6 +324,13 @@ def lib():
             "txv_pool_sent_by": ([vp, vp, vp, u32, vp, u32, vp], ctypes.c_int),
             "txv_pool_ticket_sent_by": ([vp, vp, ctypes.c_uint64, vp, u32, vp], ctypes.c_int),
             "txv_pool_senders_stats": ([vp, vp], ctypes.c_int),
+            "txv_load_commits_bytes": ([u32, ctypes.c_uint64], ctypes.c_uint64),
+            "txv_load_commits_submit": ([vp, vp, ctypes.c_uint64, vp, vp, u32, vp, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "txv_load_commits_wait": ([vp, ctypes.c_uint64, vp, vp, vp, vp, vp], ctypes.c_int),
+            "txv_load_commits": ([vp, vp, ctypes.c_uint64, vp, vp, u32, vp, ctypes.c_uint64, vp, vp, vp, vp, vp],
+                                 ctypes.c_int),
+            "txv_load_commits_ms": ([vp, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("TXV_LIB_PATH") and not hasattr(L, name):
@@ -339,7 +367,8 @@ EXPORTED_SYMBOLS = [
     "txv_scalarmult_base",
     "txv_sign_txs_meta", "txv_pool_check_routed_submit", "txv_pool_check_routed", "txv_submit_routed_checked",
     "txv_pool_check_submit_from", "txv_pool_check_from", "txv_pool_check_keys_from", "txv_pool_receive_from",
-    "txv_ingest_decode_from", "txv_pool_sent_by", "txv_pool_ticket_sent_by", "txv_pool_senders_stats"]
+    "txv_ingest_decode_from", "txv_pool_sent_by", "txv_pool_ticket_sent_by", "txv_pool_senders_stats",
+    "txv_load_commits_bytes", "txv_load_commits_submit", "txv_load_commits_wait", "txv_load_commits", "txv_load_commits_ms"]
 
 
 # ------------------------------------------------------------------ host-only helpers
@@ -488,6 +517,57 @@ class TxBatch:
 def sign_txs_bytes(n: int) -> int:
     """txv_sign_txs_bytes: the size of the route buffer Context.sign_txs writes for n txs"""
     return int(lib().txv_sign_txs_bytes(n))
+
+
+def load_commits_bytes(max_votes: int, commit_bytes: int) -> int:
+    """txv_load_commits_bytes: the route buffer Context.load_commits needs for at most max_votes
+    CommitSigs out of records of commit_bytes bytes in all"""
+    return int(lib().txv_load_commits_bytes(max_votes, commit_bytes))
+
+
+class CommitRecords:
+    """n stored Commit records (TxStore "C:%X" values) in one host buffer: record k is the
+    length[k] bytes at recs[off[k]:].  From a list of bytes, or from what Context.store_records /
+    store_records_raw returned (the Commit part of each SaveTx record, in place)."""
+
+    def __init__(self, records=(), *, recs=None, off=None, length=None):
+        if recs is not None:
+            self.recs = np.ascontiguousarray(recs, np.uint8)
+            self.off = np.ascontiguousarray(off, np.uint64)
+            self.length = np.ascontiguousarray(length, np.uint32)
+        elif len(records) and isinstance(records[0], tuple):   # Context.store_records: (sid, H-key, set, C-key, Commit)
+            self.__init__([r[4] for r in records])
+            return
+        else:
+            self.recs = np.frombuffer(b"".join(records) or b"\0", np.uint8)
+            self.length = np.array([len(r) for r in records], np.uint32)
+            self.off = (np.cumsum(self.length, dtype=np.uint64) - self.length).astype(np.uint64)
+        self.n = len(self.length)
+        self.nbytes = int(self.recs.size) if self.n else 0
+
+    @classmethod
+    def from_store_raw(cls, buf, off, lens):
+        """Context.store_records_raw's (buffer, offsets, part lengths): record k's Commit part starts
+        at off[k] + lens[k, 0] + lens[k, 1] + lens[k, 2] and is lens[k, 3] bytes long"""
+        lens = np.asarray(lens, np.uint32).reshape(-1, 4)
+        o = np.asarray(off, np.uint64) + lens[:, :3].sum(axis=1, dtype=np.uint64)
+        return cls(recs=buf, off=o, length=lens[:, 3])
+
+    def record(self, k: int) -> bytes:
+        o = int(self.off[k])
+        return self.recs[o:o + int(self.length[k])].tobytes()
+
+
+@dataclass
+class LoadedCommits:
+    """Context.load_commits_wait: the buffer's meta (what submit_routed takes), each record's
+    COMMIT_* status, first_vote [n + 1] (record k's votes are first_vote[k] .. first_vote[k + 1] - 1)
+    and Commit.TxHash of each record as (offset into the records' buffer, length)"""
+    meta: np.void
+    rec_status: np.ndarray
+    first_vote: np.ndarray
+    txhash_off: np.ndarray
+    txhash_len: np.ndarray
 
 
 def route_flags(batch: VoteBatch) -> int:
@@ -1100,6 +1180,66 @@ class Context:
         """device time (ms) of the last waited sign chain"""
         ms = ctypes.c_float()
         self._chk(lib().txv_sign_txs_ms(self._h, ctypes.byref(ms)), "txv_sign_txs_ms")
+        return ms.value
+
+    @staticmethod
+    def _commit_records(records) -> "CommitRecords":
+        if isinstance(records, CommitRecords):
+            return records
+        if isinstance(records, tuple) and len(records) == 4 and isinstance(records[0], np.ndarray):
+            return CommitRecords.from_store_raw(records[0], records[1], records[2])   # store_records_raw's
+        return CommitRecords(list(records))
+
+    def load_commits_submit(self, records, dst_ptr: int, cap: int) -> int:
+        """txv_load_commits_submit: TxStore.LoadTxCommit for a batch of stored Commit records (a list
+        of bytes, a CommitRecords, or what store_records / store_records_raw returned), decoded on
+        the GPU into one route buffer (ROUTE_TXKEY | ROUTE_NIL) at device address dst_ptr (dst_ptr
+        and cap multiples of 16).  Returns a load ticket without waiting for the GPU; up to
+        LOAD_RING in flight (TXV_ESTATE beyond)."""
+        cr = self._commit_records(records)
+        t = ctypes.c_uint64()
+        self._chk(lib().txv_load_commits_submit(self._h, cr.recs.ctypes.data, cr.nbytes, cr.off.ctypes.data,
+                                                cr.length.ctypes.data, cr.n, ctypes.c_void_p(dst_ptr), cap,
+                                                ctypes.byref(t)), "txv_load_commits_submit")
+        self._load_n = getattr(self, "_load_n", {})
+        self._load_n[t.value] = cr.n
+        return t.value
+
+    def load_commits_wait(self, ticket: int) -> "LoadedCommits":
+        """txv_load_commits_wait: a LoadedCommits once the buffer is written.  LoadCommitsError with
+        rc = E_CAPACITY (and the needed sizes) when the buffer does not fit the submit's cap."""
+        n = getattr(self, "_load_n", {}).pop(ticket, 0)
+        meta = np.zeros(1, ROUTE_META_DTYPE)
+        st = np.zeros(max(n, 1), np.uint8); first = np.zeros(n + 1, np.uint32)
+        tho = np.zeros(max(n, 1), np.uint64); thl = np.zeros(max(n, 1), np.uint32)
+        rc = lib().txv_load_commits_wait(self._h, ticket, meta.ctypes.data, st.ctypes.data, first.ctypes.data,
+                                         tho.ctypes.data, thl.ctypes.data)
+        if rc < 0:
+            cap = rc == E_CAPACITY
+            raise LoadCommitsError("txv_load_commits_wait", rc, lib().txv_last_error(self._h).decode(),
+                                   meta[0] if cap else None, st[:n] if cap else None, first if cap else None)
+        return LoadedCommits(meta[0], st[:n], first, tho[:n], thl[:n])
+
+    def load_commits(self, records, dst_ptr: int, cap: int) -> "LoadedCommits":
+        """txv_load_commits: load_commits_submit + load_commits_wait"""
+        cr = self._commit_records(records)
+        n = cr.n
+        meta = np.zeros(1, ROUTE_META_DTYPE)
+        st = np.zeros(max(n, 1), np.uint8); first = np.zeros(n + 1, np.uint32)
+        tho = np.zeros(max(n, 1), np.uint64); thl = np.zeros(max(n, 1), np.uint32)
+        rc = lib().txv_load_commits(self._h, cr.recs.ctypes.data, cr.nbytes, cr.off.ctypes.data, cr.length.ctypes.data, n,
+                                    ctypes.c_void_p(dst_ptr), cap, meta.ctypes.data, st.ctypes.data, first.ctypes.data,
+                                    tho.ctypes.data, thl.ctypes.data)
+        if rc < 0:
+            cap_err = rc == E_CAPACITY
+            raise LoadCommitsError("txv_load_commits", rc, lib().txv_last_error(self._h).decode(),
+                                   meta[0] if cap_err else None, st[:n] if cap_err else None, first if cap_err else None)
+        return LoadedCommits(meta[0], st[:n], first, tho[:n], thl[:n])
+
+    def load_commits_ms(self) -> float:
+        """device time (ms) of the last waited load's kernels"""
+        ms = ctypes.c_float()
+        self._chk(lib().txv_load_commits_ms(self._h, ctypes.byref(ms)), "txv_load_commits_ms")
         return ms.value
 
     def scalarmult_base(self, scalars) -> np.ndarray:

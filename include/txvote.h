@@ -592,6 +592,66 @@ int txv_sign_txs_meta(txv_ctx* ctx, uint32_t n, uint32_t signer, txv_route_meta*
  * value below 2^253; TXV_EINVAL above, TXV_ESTATE without a validator set) */
 int txv_scalarmult_base(txv_ctx* ctx, const uint8_t* scalars32, uint32_t n, uint8_t* enc_out);
 
+/* ---- LoadTxCommit by batch on the device: stored Commits back into TxFlow ----
+ * <- TxStore.LoadTxCommit (tx/store.go:67-80), reached from TxFlow.LoadCommit
+ * (txflow/service.go:115-120), for a batch of stored Commit records: the bytes
+ * cdc.MustMarshalBinaryBare(set.MakeCommit()) that SaveTx wrote under "C:%X" (tx/store.go:83-107) --
+ * what txv_make_commit, txv_save_tx_bytes and the store sink produce -- decoded on the GPU into ONE
+ * route buffer at dst_dev (the layout of txv_route_admitted, flags TXV_ROUTE_TXKEY | TXV_ROUTE_NIL).
+ * Record k's CommitSigs are the consecutive votes first_vote[k] .. first_vote[k + 1] - 1, in the
+ * order the record lists them.  txv_submit_routed on that buffer re-verifies every signature and
+ * re-tallies every set: the restore of committed sets after txv_reset_flow or a restart, and the
+ * check of a Commit received from elsewhere.  The load itself reads and writes no TxFlow state and
+ * needs no validator set.  The database read stays the caller's, as the write does.
+ *
+ * The decode rules are csrc/load_dev.h's header (amino as restated in oracle/wire.c; PARITY UNPINNED
+ * beyond the records this library and the oracle write).  Per record, rec_status:
+ *   TXV_COMMIT_OK       decoded; TXV_COMMIT_CORRUPT  an amino error in the envelope or in any
+ *   element (LoadTxCommit panics): the record gives no votes; TXV_COMMIT_EMPTY  length 0 (db.Get
+ *   found nothing, LoadTxCommit returns nil): no votes.
+ * A zero-length element is a nil *CommitSig: is_nil = 1, every other column zero.  A vote carries its
+ * CommitSig's own TxHash, not the enclosing Commit's (the reference compares neither with the
+ * other).  sig_len > 64 and addr_len > 20 keep their true lengths with the first 64 / 20 bytes.
+ *
+ * recs: host memory; record k is the len[k] bytes at recs + off[k], at any alignment (off[k] +
+ * len[k] <= recs_bytes; recs_bytes < 2^32, as for txv_decode_msgs).  A txv_store_records read-out can
+ * be passed as it is: record k's Commit part is at off_out[k] + lens[4k] + lens[4k+1] + lens[4k+2],
+ * lens[4k+3] bytes long.  The bytes are uploaded through the ring entry's pinned staging and may be
+ * reused once the submit returns; from registered memory (txv_host_register) they are uploaded
+ * directly and must stay unchanged until the wait.
+ *
+ * txv_load_commits_bytes(max_votes, commit_bytes) = txv_route_bytes(max_votes, commit_bytes,
+ * TXV_ROUTE_TXKEY | TXV_ROUTE_NIL); with commit_bytes = the sum of the len[k] it bounds the arena of
+ * any input these encoders wrote (every TxHash byte of the arena is a byte of some record).  dst_dev and cap must be
+ * multiples of 16 (TXV_EINVAL otherwise, as from the route calls).  The buffer's size is decided on
+ * the device: when it exceeds cap nothing is written to dst_dev at all, the wait returns
+ * TXV_ECAPACITY, and *meta_out carries the true n, arena_bytes and bytes with reserved = 1
+ * (txv_route_admitted's convention); rec_status and first_vote are valid all the same.
+ *
+ * A ring of TXV_LOAD_RING loads in flight, ticket t on entry (t - 1) % TXV_LOAD_RING, waits in any
+ * order; a submit into an entry that holds an unwaited ticket returns TXV_ESTATE and changes
+ * nothing, as does a wait for a ticket not in flight.  txv_sync, txv_reset_flow and txv_destroy wait
+ * for the loads in flight first.  The chain runs on the context's copy and key streams.
+ * Outputs of the wait (each may be NULL): meta_out; rec_status [n_records]; first_vote
+ * [n_records + 1]; rec_txhash_off / rec_txhash_len [n_records]: Commit.TxHash as an offset into recs
+ * and a length (0 when the field is absent or the record is not OK).  The wait takes n_records from
+ * the submit.  txv_load_commits is submit + wait. */
+#define TXV_COMMIT_OK 0
+#define TXV_COMMIT_CORRUPT 1
+#define TXV_COMMIT_EMPTY 2
+#define TXV_LOAD_RING 2
+uint64_t txv_load_commits_bytes(uint32_t max_votes, uint64_t commit_bytes);
+int txv_load_commits_submit(txv_ctx* ctx, const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off,
+                            const uint32_t* len, uint32_t n_records, void* dst_dev, uint64_t cap,
+                            uint64_t* load_ticket);
+int txv_load_commits_wait(txv_ctx* ctx, uint64_t load_ticket, txv_route_meta* meta_out, uint8_t* rec_status,
+                          uint32_t* first_vote, uint64_t* rec_txhash_off, uint32_t* rec_txhash_len);
+int txv_load_commits(txv_ctx* ctx, const uint8_t* recs, uint64_t recs_bytes, const uint64_t* off, const uint32_t* len,
+                     uint32_t n_records, void* dst_dev, uint64_t cap, txv_route_meta* meta_out, uint8_t* rec_status,
+                     uint32_t* first_vote, uint64_t* rec_txhash_off, uint32_t* rec_txhash_len);
+/* measurement: device time (ms) of the last waited load's kernels, like txv_sign_txs_ms */
+int txv_load_commits_ms(txv_ctx* ctx, float* ms);
+
 /* device pointer + byte size of the per-set committed bitmap (1 bit per tx-set id) */
 int txv_commit_bitmap(txv_ctx* ctx, void** dev_ptr, uint64_t* bytes);
 /* device-to-device copy of the commit bitmap into caller device memory (e.g. an RCCL buffer) */
