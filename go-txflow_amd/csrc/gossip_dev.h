@@ -9,7 +9,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "amino.hpp"
+#include "txvote_lanes.h"
 
 #ifndef TXV_GOSSIP_OK               // (include/txvote.h)
 #define TXV_GOSSIP_OK 0
@@ -19,15 +19,13 @@
 
 namespace txv_gossip {
 
-constexpr uint32_t kLanes = 16;     // lanes that share one message
+using txv_lanes::kLanes, txv_lanes::LaneWords, txv_lanes::lane_words, txv_lanes::Tile, txv_lanes::VoteLayout;
 
-// where the fields of one encodable message (flag TXV_GOSSIP_OK: every length fits 32 bits) start,
-// as byte offsets from the message's first byte
+// where the bytes of one encodable message (flag TXV_GOSSIP_OK: every length fits 32 bits) are
 struct MsgLayout {
-  uint32_t body;                    // TxVote bare body length (= txvote_size)
   uint32_t len;                     // whole message
-  uint32_t p_h, p_th, p_key, p_tk, p_tm, p_ad, p_sg;   // Height, TxHash field, TxHash bytes, TxKey, Timestamp, address, signature
-  uint32_t tlen;                    // time body length (0: no Timestamp field)
+  uint32_t base;                    // the TxVote bare body starts here: behind 4 prefix bytes, 0x0a, uvarint(body)
+  VoteLayout v;                     // the body's fields, from there
 };
 
 // The length pass measures a non-nil batch entry once: its flag, the bytes its message takes in
@@ -61,90 +59,26 @@ TXV_AHD uint32_t msg_measure(int64_t height, uint32_t hl, int64_t sec, int32_t n
 TXV_AHD MsgLayout msg_layout(uint64_t lay, uint32_t len, uint32_t* hl_out, uint32_t* al_out, uint32_t* sl_out) {
   const uint32_t hl = (uint32_t)lay, w = (uint32_t)(lay >> 32);
   const uint32_t ub = w & 7u, f_h = (w >> 3) & 15u, tl = (w >> 7) & 31u, al = (w >> 12) & 31u, sl = (w >> 17) & 127u;
-  uint32_t uh = 0;                                         // uvarint(hl) bytes
-  for (uint32_t v = hl; v; v >>= 7) ++uh;
   MsgLayout L;
   L.len = len;
-  L.body = len - 5u - ub;
-  L.tlen = tl;
-  L.p_h = 5u + ub;
-  L.p_th = L.p_h + f_h;
-  L.p_key = L.p_th + (hl ? 1u + uh : 0u);
-  L.p_tk = L.p_key + hl;
-  L.p_tm = L.p_tk + 34u;
-  L.p_ad = L.p_tm + (tl ? 2u + tl : 0u);
-  L.p_sg = L.p_ad + (al ? 2u + al : 0u);
+  L.base = 5u + ub;
+  L.v = txv_lanes::vote_layout(f_h, hl, tl, al, sl);
   *hl_out = hl; *al_out = al; *sl_out = sl;
   return L;
 }
 
-// the tile holding message bytes [t0, t0 + n): stores outside it are dropped
-struct Tile {
-  uint8_t* p;
-  uint32_t t0, n;
-  TXV_AHD void put(uint32_t x, uint32_t byte) const {
-    const uint32_t o = x - t0;
-    if (o < n) p[o] = (uint8_t)byte;
-  }
-  // the first `nb` (<= 4) bytes of the little-endian word w
-  TXV_AHD void put_word(uint32_t x, uint32_t w, uint32_t nb) const {
-    for (uint32_t i = 0; i < 4; ++i)
-      if (i < nb) put(x + i, w >> (8 * i));
-  }
-  TXV_AHD uint32_t put_uv(uint32_t x, uint64_t v) const {
-    uint32_t k = 0;
-#pragma clang loop unroll(disable)
-    for (; v >= 0x80; v >>= 7, ++k) put(x + k, (uint32_t)v | 0x80u);
-    put(x + k, (uint32_t)v);
-    return k + 1;
-  }
-};
-
-// the words lane q gathers for its message before it writes (independent loads): signature word q,
-// TxKey word q & 7 (zero without a TxKey column), address word min(q, 4).  The columns are 4-byte
-// aligned rows of 64 / 32 / 20 bytes.
-struct LaneWords { uint32_t sw, tw, aw; };
-TXV_AHD LaneWords lane_words(uint32_t q, const uint8_t* sig, const uint8_t* txkey, const uint8_t* addr) {
-  LaneWords w;
-  w.sw = reinterpret_cast<const uint32_t*>(sig)[q];
-  w.tw = txkey ? reinterpret_cast<const uint32_t*>(txkey)[q & 7u] : 0u;
-  w.aw = reinterpret_cast<const uint32_t*>(addr)[q < 4u ? q : 4u];
-  return w;
-}
-
 // Lane q of the kLanes that share a message (flag TXV_GOSSIP_OK, layout L, len16 = its length
-// rounded up to 16) writes its part of the bytes into the tile: its signature word, TxKey word
-// (lanes 0 - 7), address word (lanes 0 - 4), the prefix, tags and varints (lanes 8 - 10), every
-// 16th TxHash byte of the tile's range, and one byte of the zero padding.
+// rounded up to 16) writes its part of the bytes into the tile: the message header (lane 8), its
+// part of the TxVote body (txvote_lanes.h: put_vote) and one byte of the zero padding.
 TXV_AHD void put_msg(const Tile& tl, const MsgLayout& L, uint32_t q, uint32_t prefix, int64_t height, int64_t sec,
                      int32_t nanos, const uint8_t* th, uint32_t hl, uint32_t al, uint32_t sl, const LaneWords& w) {
-  const uint32_t len = L.len;
-  if (4u * q < sl) tl.put_word(L.p_sg + 2u + 4u * q, w.sw, sl - 4u * q);
-  if (q < 8) tl.put_word(L.p_tk + 2u + 4u * q, w.tw, 4);
-  if (q < 5 && 4u * q < al) tl.put_word(L.p_ad + 2u + 4u * q, w.aw, al - 4u * q);
   if (q == 8) {
     tl.put_word(0, prefix, 4);
     tl.put(4, 0x0a);
-    tl.put_uv(5, L.body);
-    if (height != 0) { tl.put(L.p_h, 0x08); tl.put_uv(L.p_h + 1u, (uint64_t)height); }
-  } else if (q == 9) {
-    if (hl) { tl.put(L.p_th, 0x12); tl.put_uv(L.p_th + 1u, hl); }
-    tl.put(L.p_tk, 0x1a); tl.put(L.p_tk + 1u, 0x20);
-    if (al) { tl.put(L.p_ad, 0x2a); tl.put(L.p_ad + 1u, al); }
-    if (sl) { tl.put(L.p_sg, 0x32); tl.put(L.p_sg + 1u, sl); }
-  } else if (q == 10 && L.tlen > 0) {
-    tl.put(L.p_tm, 0x22); tl.put(L.p_tm + 1u, L.tlen);
-    uint32_t p = L.p_tm + 2u;
-    if (sec != 0) { tl.put(p, 0x08); p += 1u + tl.put_uv(p + 1u, (uint64_t)sec); }
-    if (nanos != 0) { tl.put(p, 0x10); tl.put_uv(p + 1u, (uint64_t)(uint32_t)nanos); }
+    tl.put_uv(5, L.v.size);
   }
-  // the TxHash bytes that fall into the tile
-  const uint32_t t1 = tl.t0 + tl.n;
-  const uint32_t lo = tl.t0 > L.p_key ? tl.t0 - L.p_key : 0u;
-  const uint32_t hi = t1 > L.p_key ? (t1 - L.p_key < hl ? t1 - L.p_key : hl) : 0u;
-#pragma clang loop unroll_count(4)
-  for (uint32_t i = lo + q; i < hi; i += kLanes) tl.put(L.p_key + i, th[i]);
-  tl.put(len + q, 0);               // pad: fewer than 16 bytes, and the tile ends at len16 at the latest
+  txv_lanes::put_vote(tl, L.base, L.v, q, height, sec, nanos, th, hl, al, sl, w);
+  tl.put(L.len + q, 0);             // pad: fewer than 16 bytes, and the tile ends at len16 at the latest
 }
 
 }  // namespace txv_gossip

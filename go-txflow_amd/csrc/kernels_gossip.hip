@@ -11,7 +11,7 @@
 //
 // The chain reads only the slot's raw columns (height, ts_sec, ts_nanos, th_off, th_len, th, addr,
 // addr_len, sig_raw, sig_len, nil, txkey) and no TxFlow state; every producer -> consumer pair is a
-// launch apart:
+// launch apart (len and apply are arrival_list.h's scan):
 //   len     one lane per entry: flag, message length and the packed field lengths the layout
 //           follows from (nil: not listed), and per 1024 arrival indices the listed entries and
 //           their bytes, each rounded up to 16
@@ -24,93 +24,55 @@
 //           or entries is not written at all.
 #include <algorithm>
 
-#include "block_scan.h"
+#include "arrival_list.h"
 #include "gossip_dev.h"
-#include "txv_flow.h"
 
 namespace {
 
-constexpr uint32_t kGsItems = 1024;    // arrival indices per scan block (256 threads x 4 consecutive)
 constexpr uint32_t kGsTile = 512;      // LDS tile bytes per message
 constexpr uint64_t kGsListed = 1ull << 63;
 
-// entry i's scratch word: listed << 63 | flag << 32 | length (0: a nil entry, or past the batch)
+// entry i's scratch word: listed << 63 | flag << 32 | length (0: a nil entry)
 // (*lay: the field lengths of an encodable message, gossip_dev.h msg_measure)
 __device__ __forceinline__ uint64_t gs_entry(const FlowBatch& b, uint32_t i, uint64_t* lay) {
   *lay = 0;
-  if (i >= b.n || (b.nil && b.nil[i])) return 0;
+  if (b.nil && b.nil[i]) return 0;
   uint32_t len;
   const uint32_t flag = txv_gossip::msg_measure(b.height[i], b.th_len[i], b.ts_sec[i], b.ts_nanos[i], b.addr_len[i],
                                                 b.sig_len[i], &len, lay);
   return kGsListed | ((uint64_t)flag << 32) | len;
 }
-__device__ __forceinline__ uint64_t gs_padded(uint64_t e) { return ((e & 0xFFFFFFFFull) + 15ull) & ~15ull; }
+// a non-nil entry is listed; its weight: the message length rounded up to 16; its word: the entry's
+__device__ __forceinline__ ListValue gs_value(uint64_t e) { return ListValue{(e >> 63) != 0, ((e & 0xFFFFFFFFull) + 15ull) & ~15ull, e}; }
 
+// len: measures every entry on the way
 __global__ void __launch_bounds__(256) txv_k_gs_len(FlowBatch b, GossipSink k) {
-  const uint32_t base = blockIdx.x * kGsItems + 4u * threadIdx.x;
-  uint64_t bytes = 0, ents = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
+  list_count(b.n, k.blk, [&](uint32_t i) {
     uint64_t lay;
-    const uint64_t e = gs_entry(b, base + q, &lay);
-    if (base + q < b.n) {
-      k.ent[base + q] = e;
-      k.lay[base + q] = lay;
-    }
-    bytes += gs_padded(e);
-    ents += e >> 63;
-  }
-  uint64_t tb, te;
-  (void)block_excl_scan64(bytes, &tb);
-  (void)block_excl_scan64(ents, &te);
-  if (threadIdx.x == 0) {
-    k.blk[2 * (size_t)blockIdx.x] = te;
-    k.blk[2 * (size_t)blockIdx.x + 1] = tb;
-  }
+    const uint64_t e = gs_entry(b, i, &lay);
+    k.ent[i] = e;
+    k.lay[i] = lay;
+    return gs_value(e);
+  });
 }
 
-// exclusive scan over the arrival indices, as txv_k_st_apply (each block sums the block counts
-// before its own): the descriptor of entry r of the batch; blk[2 nb ..] = (entries, bytes) and the
-// result words.  n == 0: one block, which only writes those.
+// apply: the descriptor of entry r of the batch; the result words
 __global__ void __launch_bounds__(256) txv_k_gs_apply(FlowBatch b, GossipSink k, uint32_t nb) {
-  uint64_t pe = 0, pb = 0;
-  for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 256) {
-    pe += k.blk[2 * (size_t)j];
-    pb += k.blk[2 * (size_t)j + 1];
-  }
-  uint64_t before_e, before_b;
-  (void)block_excl_scan64(pe, &before_e);
-  (void)block_excl_scan64(pb, &before_b);
-  const uint32_t base = blockIdx.x * kGsItems + 4u * threadIdx.x;
-  uint64_t e[4], bytes = 0, ents = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    e[q] = base + q < b.n ? k.ent[base + q] : 0ull;
-    bytes += gs_padded(e[q]);
-    ents += e[q] >> 63;
-  }
-  uint64_t tot_e, tot_b;
-  uint64_t run_e = before_e + block_excl_scan64(ents, &tot_e);
-  uint64_t run_b = before_b + block_excl_scan64(bytes, &tot_b);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (e[q] >> 63) {
-      if (run_e < k.cap_msgs) {
+  uint64_t n_e, n_b;
+  const bool last = list_apply(
+      b.n, nb, k.blk, [&](uint32_t i) { return gs_value(k.ent[i]); },
+      [&](uint32_t i, uint64_t r, uint64_t off, const ListValue& x) {
+        if (r >= k.cap_msgs) return;
+        const uint64_t e = x.word;
         GossipDesc d;
-        d.off_lo = (uint32_t)run_b | ((uint32_t)(e[q] >> 32) & 15u);
-        d.off_hi = (uint32_t)(run_b >> 32);
-        d.len = (uint32_t)e[q];
-        d.idx = base + q;
-        *reinterpret_cast<uint4*>(k.desc + run_e) = make_uint4(d.off_lo, d.off_hi, d.len, d.idx);
-      }
-      ++run_e;
-      run_b += gs_padded(e[q]);
-    }
-  }
-  if (blockIdx.x + 1 == gridDim.x && threadIdx.x == 0) {
-    const uint64_t n_e = before_e + tot_e, n_b = before_b + tot_b;
-    k.blk[2 * (size_t)nb] = n_e;                  // (no block reads index nb)
-    k.blk[2 * (size_t)nb + 1] = n_b;
+        d.off_lo = (uint32_t)off | ((uint32_t)(e >> 32) & 15u);
+        d.off_hi = (uint32_t)(off >> 32);
+        d.len = (uint32_t)e;
+        d.idx = i;
+        *reinterpret_cast<uint4*>(k.desc + r) = make_uint4(d.off_lo, d.off_hi, d.len, d.idx);
+      },
+      &n_e, &n_b);
+  if (last) {
     uint4* res = reinterpret_cast<uint4*>(k.result);
     res[0] = make_uint4((uint32_t)n_e, (n_e > k.cap_msgs || n_b > k.cap_bytes) ? 1u : 0u, 0u, 0u);
     res[1] = make_uint4((uint32_t)n_b, (uint32_t)(n_b >> 32), 0u, 0u);
@@ -174,8 +136,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) tx
 }  // namespace
 
 extern "C" hipError_t txv_flow_gossip_msgs(const FlowBatch* b, GossipSink k, hipStream_t st) {
-  const uint32_t nb = (b->n + kGsItems - 1) / kGsItems;
-  if (nb > 8192) return hipErrorInvalidValue;
+  uint32_t nb;
+  if (!list_blocks(b->n, &nb)) return hipErrorInvalidValue;
   if (b->n) hipLaunchKernelGGL(txv_k_gs_len, dim3(nb), dim3(256), 0, st, *b, k);
   hipLaunchKernelGGL(txv_k_gs_apply, dim3(nb ? nb : 1u), dim3(256), 0, st, *b, k, nb);
   // (an empty batch: one block, which writes the result words)

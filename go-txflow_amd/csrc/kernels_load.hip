@@ -60,32 +60,6 @@ struct LdsFill {
 };
 using Win = Window<LdsFill>;
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d, 64);
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t x) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) {
-    const uint32_t y = (uint32_t)__shfl_xor((int)x, d, 64);
-    x = y > x ? y : x;
-  }
-  return x;
-}
-// exclusive scan over the wave; *total = the wave's sum
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t x, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t inc = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)inc, d, 64);
-    if (lane >= (uint32_t)d) inc += y;
-  }
-  *total = (uint32_t)__shfl((int)inc, 63, 64);
-  return inc - x;
-}
-
 // a record's bytes read out of the window: byte p of the record is at lds[p + d] (d = the
 // record's start less the window's, modulo 2^32)
 struct LdsBytes {

@@ -22,30 +22,11 @@
 // No atomics on shared words, no host round trip between the launches.
 #include <algorithm>
 
+#include "block_scan.h"
 #include "sha2.h"
 #include "route.h"
 
 namespace {
-
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// exclusive prefix sum over the wave's lanes
-__device__ __forceinline__ uint32_t wave_excl(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-  uint32_t x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x - v;
-}
 
 // a vote's TxHash length as routed: a nil vote carries none
 __device__ __forceinline__ uint32_t routed_len(const RouteArgs& a, uint32_t i) {
@@ -95,7 +76,7 @@ __global__ void __launch_bounds__(1024) txv_k_route_scan(RouteArgs a) {
     const uint32_t w = base + threadIdx.x;
     const uint32_t c = w < a.nw ? a.wcnt[(size_t)w * a.G + s] : 0u;
     const uint32_t b = w < a.nw ? a.wbytes[(size_t)w * a.G + s] : 0u;
-    const uint32_t ec = wave_excl(c), eb = wave_excl(b);
+    const uint32_t ec = wave_excl_scan(c), eb = wave_excl_scan(b);
     if (lane == 63) { sc[wv] = ec + c; sb[wv] = eb + b; }
     __syncthreads();
     uint32_t pc = carry_c, pb = carry_b, tc = 0, tb = 0;
@@ -153,7 +134,7 @@ __global__ void __launch_bounds__(256) txv_k_route_scatter(RouteArgs a) {
     const bool mine = r == s;
     const uint64_t m = __ballot(mine);
     if (!m) continue;
-    const uint32_t e = wave_excl(mine ? len : 0u);
+    const uint32_t e = wave_excl_scan(mine ? len : 0u);
     if (mine) {
       rank = (uint32_t)__popcll(m & below);
       brank = e;

@@ -9,105 +9,61 @@
 // the batch ADDED a vote to, set_cross tells which of them fired, a cell's candidate word carries
 // the arrival index of its ADDED vote of this batch, its acc the arena row of its accepted vote.
 //
-// The chain (flow stream, behind the tally; every producer -> consumer pair is a launch apart):
+// The chain (flow stream, behind the tally; every producer -> consumer pair is a launch apart;
+// sets, count and apply are arrival_list.h's walk and scan):
 //   sets    one wave per stamped set: a fired set's accepted-vote count and its id are stored at
 //           the arrival index of its last fired vote (unique per set: a vote belongs to one set),
 //           tagged with the batch stamp, so the columns are never cleared
-//   count   per 1024 arrival indices: (fired sets << 32 | entries)
-//   apply   exclusive scan over the indices (each block sums the block counts before it): fired
-//           set k of the list and its first entry; the result words (mapped host memory)
+//   count   per 1024 arrival indices: the fired sets and their entries
+//   apply   exclusive scan over the indices: fired set k of the list and its first entry; the
+//           result words (mapped host memory)
 //   emit    one block per fired set: its accepted rows sorted by sequence number in LDS, then the
 //           signature rows (16 lanes per 64-byte row), lengths, TxVote.Size() and set ids written
 //           at first entry + rank; nothing at or past the sink's capacity
 #include <algorithm>
 
 #include "amino.hpp"
-#include "block_scan.h"
-#include "txv_flow.h"
+#include "arrival_list.h"
 
 namespace {
 
-constexpr uint32_t kUpdItems = 1024;   // arrival indices per scan block (256 threads x 4 consecutive)
-
-// this index's scan value: (1 << 32 | accepted votes) where a fired set's last fired vote arrived
-__device__ __forceinline__ uint64_t upd_value(const UpdateSink& u, uint32_t i, uint32_t n, uint32_t stamp) {
-  if (i >= n) return 0;
-  const uint64_t w = u.cnt[i];
-  return (uint32_t)(w >> 32) == stamp ? ((1ull << 32) | (uint32_t)w) : 0ull;
-}
-
-// One wave per set the batch ADDED a vote to (persistent one-wave blocks, as txv_k_tally_cross).
-// A set fired in this batch iff the crossing step left it a crossing index; its last fired vote is
-// the largest arrival index among its cells' candidates of this batch (every ADDED vote at or after
-// the crossing fires, and the crossing vote itself is one of them).
-__global__ void __launch_bounds__(64) txv_k_upd_sets(FlowState fs, FlowBatch b, const uint32_t* n_stamped, UpdateSink u) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t n_list = min(*n_stamped, b.n);
-  for (uint32_t j = blockIdx.x; j < n_list; j += gridDim.x) {
-    const uint32_t s = b.stamped[j];
-    if (s >= fs.max_txs || fs.set_cross[s] == TXV_NO_CROSS) continue;
-    const TallyCell* row = fs.cell + (size_t)s * fs.n_vals;
-    uint32_t cnt = 0, last1 = 0;                 // last1: 1 + the largest arrival index (0: none)
-    for (uint32_t v = lane; v < fs.n_vals; v += 64) {
-      const TallyCell c = row[v];
-      cnt += c.acc != 0 ? 1u : 0u;
-      const uint32_t f = cand_of(c.cand, b.stamp);
-      if (f != TXV_NONE) last1 = max(last1, f + 1u);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      cnt += (uint32_t)__shfl_xor((int)cnt, o, 64);
-      last1 = max(last1, (uint32_t)__shfl_xor((int)last1, o, 64));
-    }
-    if (lane == 0 && last1 != 0 && last1 - 1u < b.n) {
-      u.cnt[last1 - 1u] = ((uint64_t)b.stamp << 32) | cnt;
-      u.sid[last1 - 1u] = s;
-    }
+// arrival index i is listed where a fired set's last fired vote arrived; its weight: the set's accepted votes
+struct UpdValue {
+  UpdateSink u;
+  uint32_t stamp;
+  __device__ __forceinline__ ListValue operator()(uint32_t i) const {
+    const uint64_t w = u.cnt[i];
+    return ListValue{(uint32_t)(w >> 32) == stamp, (uint32_t)w};
   }
+};
+
+// sets: a fired set's accepted-vote count and its id, tagged with the batch stamp
+__global__ void __launch_bounds__(64) txv_k_upd_sets(FlowState fs, FlowBatch b, const uint32_t* n_stamped, UpdateSink u) {
+  fired_sets_walk(
+      fs, b, n_stamped, [](const TallyCell& c, uint32_t) -> uint64_t { return c.acc != 0 ? 1u : 0u; },
+      [&](uint32_t i, uint32_t s, uint32_t, uint64_t cnt) {
+        u.cnt[i] = ((uint64_t)b.stamp << 32) | (uint32_t)cnt;
+        u.sid[i] = s;
+      });
 }
 
 __global__ void __launch_bounds__(256) txv_k_upd_count(FlowBatch b, UpdateSink u) {
-  const uint32_t base = blockIdx.x * kUpdItems + 4u * threadIdx.x;
-  uint64_t x = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) x += upd_value(u, base + k, b.n, b.stamp);
-  uint64_t total;
-  (void)block_excl_scan64(x, &total);
-  if (threadIdx.x == 0) u.blk[blockIdx.x] = total;
+  list_count(b.n, u.blk, UpdValue{u, b.stamp});
 }
 
-// exclusive scan over the arrival indices: fired set k of the list and its first entry.  Each block
-// sums the block counts before its own itself (nb <= 8192: at most 32 per thread), so no launch of
-// its own computes their prefix; the last block holds the grand total and writes blk[nb] and the
-// batch's result words: entries written, fired sets, entries needed, 1 when they exceed the capacity.
-// n == 0: one block, which only writes those.
+// apply: fired set k of the list and its first entry; the batch's result words: entries written,
+// fired sets, entries needed, 1 when they exceed the capacity
 __global__ void __launch_bounds__(256) txv_k_upd_apply(FlowBatch b, UpdateSink u, uint32_t nb) {
-  uint64_t part = 0;
-  for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 256) part += u.blk[j];
-  uint64_t before;
-  (void)block_excl_scan64(part, &before);
-  const uint32_t base = blockIdx.x * kUpdItems + 4u * threadIdx.x;
-  uint64_t x[4], sum = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    x[k] = upd_value(u, base + k, b.n, b.stamp);
-    sum += x[k];
-  }
-  uint64_t total;
-  uint64_t run = before + block_excl_scan64(sum, &total);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (x[k]) {
-      const uint32_t rank = (uint32_t)(run >> 32);     // < fired sets <= n
-      u.fired[2 * (size_t)rank] = u.sid[base + k];
-      u.fired[2 * (size_t)rank + 1] = (uint32_t)run;
-    }
-    run += x[k];
-  }
-  if (blockIdx.x + 1 == gridDim.x && threadIdx.x == 0) {
-    const uint64_t all = before + total;
-    u.blk[nb] = all;                                   // (no block reads index nb)
-    const uint32_t need = (uint32_t)all, sets = (uint32_t)(all >> 32);
+  uint64_t n_sets, n_entries;
+  const bool last = list_apply(
+      b.n, nb, u.blk, UpdValue{u, b.stamp},
+      [&](uint32_t i, uint64_t rank, uint64_t first, const ListValue&) {
+        u.fired[2 * (size_t)rank] = u.sid[i];
+        u.fired[2 * (size_t)rank + 1] = (uint32_t)first;
+      },
+      &n_sets, &n_entries);
+  if (last) {
+    const uint32_t need = (uint32_t)n_entries, sets = (uint32_t)n_sets;
     *reinterpret_cast<uint4*>(u.result) = make_uint4(min(need, u.cap), sets, need, need > u.cap ? 1u : 0u);
   }
 }
@@ -127,7 +83,7 @@ __global__ void __launch_bounds__(T) txv_k_upd_emit(FlowState fs, UpdateSink u, 
   __shared__ uint32_t l_row[Cap];
   __shared__ uint32_t l_k;
   const uint32_t t = threadIdx.x;
-  const uint32_t n_fired = (uint32_t)(u.blk[nb] >> 32);
+  const uint32_t n_fired = (uint32_t)u.blk[2 * (size_t)nb];
   const size_t M = fs.max_accepted;
   // kPer blocks per set: each lists and sorts the whole set (cheap) and writes T of its entries
   for (uint32_t work = blockIdx.x; work < n_fired * (uint32_t)kPer; work += gridDim.x) {
@@ -141,8 +97,7 @@ __global__ void __launch_bounds__(T) txv_k_upd_emit(FlowState fs, UpdateSink u, 
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const uint32_t v = t + (uint32_t)i * T;          // n_vals <= Cap = kPer * T
-      acc[i] = v < fs.n_vals ? row[v].acc : 0u;
-      if (acc[i] > fs.max_accepted) acc[i] = 0;
+      acc[i] = v < fs.n_vals ? acc_of(fs, row[v].acc) : 0u;
     }
 #pragma unroll
     for (int i = 0; i < kPer; ++i) sq[i] = acc[i] ? fs.arena_seq[acc[i] - 1] : 0ull;
@@ -207,8 +162,8 @@ __global__ void __launch_bounds__(T) txv_k_upd_emit(FlowState fs, UpdateSink u, 
 extern "C" hipError_t txv_flow_update_list(const FlowState* fs, const FlowBatch* b, const uint32_t* n_stamped,
                                            UpdateSink u, hipStream_t st) {
   if (fs->n_vals > TXV_UPD_MAX_VALS) return hipErrorInvalidValue;
-  const uint32_t nb = (b->n + kUpdItems - 1) / kUpdItems;
-  if (nb > 8192) return hipErrorInvalidValue;
+  uint32_t nb;
+  if (!list_blocks(b->n, &nb)) return hipErrorInvalidValue;
   if (b->n) {
     const uint32_t waves = std::min<uint32_t>(b->n, 4096u);
     hipLaunchKernelGGL(txv_k_upd_sets, dim3(waves), dim3(64), 0, st, *fs, *b, n_stamped, u);

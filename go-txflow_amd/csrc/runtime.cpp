@@ -2645,7 +2645,7 @@ int txv_update_sink_enable(txv_ctx* c, uint32_t max_entries) {
     if (m && !s.cons_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.cons_ev, hipEventDisableTiming));
   }
   if ((r = dalloc(c, &u.d_cnt, m ? nb : 0)) || (r = dalloc(c, &u.d_sid, m ? nb : 0)) ||
-      (r = dalloc(c, &u.d_blk, m ? (nb + 1023) / 1024 + 1 : 0)) || (r = dalloc(c, &u.d_fired, m ? 2 * nb : 0)) ||
+      (r = dalloc(c, &u.d_blk, m ? 2 * ((nb + 1023) / 1024 + 1) : 0)) || (r = dalloc(c, &u.d_fired, m ? 2 * nb : 0)) ||
       (r = dalloc(c, &u.d_keys, 8 * m)))
     return r;
   if (!m) return TXV_OK;

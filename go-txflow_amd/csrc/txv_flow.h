@@ -219,7 +219,7 @@ struct UpdateSink {
   uint64_t* cnt;                  // [max_batch] (stamp << 32 | accepted votes) of the set whose last fired
                                   // vote arrived at this index (stamp-tagged: never cleared)
   uint32_t* sid;                  // [max_batch] that set's id
-  uint64_t* blk;                  // [ceil(max_batch / 1024) + 1] scan blocks: (fired sets << 32 | entries)
+  uint64_t* blk;                  // [ceil(max_batch / 1024) + 1][2] scan blocks: (fired sets, entries)
   uint32_t* fired;                // [max_batch][2] (set id, first entry) of the fired sets in list order
 };
 

@@ -21,7 +21,7 @@ EMU = os.path.join(EMU_DIR, "build", "libemu_gossip.so")
 @pytest.fixture(scope="module")
 def emu():
     src = os.path.join(EMU_DIR, "emu_gossip.hip")
-    deps = [src] + [os.path.join(HERE, "..", "go-txflow_amd", "csrc", f) for f in ("gossip_dev.h", "amino.hpp")]
+    deps = [src] + [os.path.join(HERE, "..", "go-txflow_amd", "csrc", f) for f in ("gossip_dev.h", "txvote_lanes.h", "amino.hpp")]
     if not os.path.exists(EMU) or any(os.path.getmtime(d) > os.path.getmtime(EMU) for d in deps):
         os.makedirs(os.path.dirname(EMU), exist_ok=True)
         subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", src, "-o", EMU], check=True)
