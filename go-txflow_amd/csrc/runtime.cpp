@@ -2001,6 +2001,21 @@ int txv_set_validators(txv_ctx* c, const uint8_t* pubs32, const int64_t* powers,
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n > c->cfg.max_validators) { c->err = "validator set exceeds max_validators"; return TXV_ECAPACITY; }
+  // tendermint's ValidatorSet panics on a negative power or a total above MaxTotalVotingPower =
+  // MaxInt64 / 8; within it total * 2 / 3 + 1 and every stake sum stay inside int64.  Refused
+  // before anything of the previous registry is touched.
+  {
+    constexpr int64_t kMaxTotal = INT64_MAX / 8;
+    int64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (powers[i] < 0) { c->err = "negative voting power"; return TXV_EINVAL; }
+      if (powers[i] > kMaxTotal - total) {
+        c->err = "total voting power exceeds INT64_MAX / 8 (tendermint MaxTotalVotingPower)";
+        return TXV_EINVAL;
+      }
+      total += powers[i];
+    }
+  }
   for (auto& e : c->sign)   // a sign in flight reads the chain id and the base-point table this call may replace
     if (e.ticket && e.ev) HIP_TRY(c, hipEventSynchronize(e.ev));
   c->n_vals = n;

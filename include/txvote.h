@@ -180,7 +180,11 @@ void txv_destroy(txv_ctx* ctx);
 const char* txv_last_error(txv_ctx* ctx);
 int  txv_device_name(txv_ctx* ctx, char* buf, uint32_t cap);
 
-/* Validator set + chain id.  pubs32: n x 32-byte ed25519 keys; powers: VotingPower.
+/* Validator set + chain id.  pubs32: n x 32-byte ed25519 keys; powers: VotingPower, each in
+ * [0, INT64_MAX / 8] with a total of at most INT64_MAX / 8 (tendermint's MaxTotalVotingPower: the
+ * reference panics beyond it): TXV_EINVAL, with txv_last_error set, for a negative power or a larger
+ * total, and the previous registry and its tally state stay as they were.  Within the range the
+ * quorum Total*2/3 + 1 and every stake sum stay inside int64.  Power 0 is accepted.
  * Builds the per-validator tables on the device (K0) for the keys that have none: the context
  * keeps each key's tables in a slot of its table pool, so a set that re-orders, adds or drops
  * validators rebuilds only the new keys (and keys that left come back without a rebuild while
